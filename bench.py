@@ -20,6 +20,8 @@ split. ``final_free_energy`` in the record is the F of the last timed step;
 exact configuration.
 
     python bench.py --gpus N --steps K --warmup W
+    python bench.py ... --dump-outputs DIR    # + the last timed step's results as DIR/*.npy
+    python bench.py ... --full                # + measurements beyond the headline (none yet)
 N > 1: run under torch.distributed.run (one rank per GPU), or directly - then
 bench.py launches the N ranks itself (fresh worker processes, started before
 this process touches the GPU). value = whole-job samples/s from the max step
@@ -70,7 +72,18 @@ def _args(argv=None):
                     help="multi-rank GEMM grid policy (parallel/runner.py DataParallelRunner)")
     ap.add_argument("--cpu", action="store_true", help="plumbing run on CPU (gloo; use tiny sizes)")
     ap.add_argument("--verbose", action="store_true")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0) as "
+                         "DIR/<name>.npy, float32; large arrays as a fixed seeded sample")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure. There are none "
+                         "yet: a plain run times the step and nothing else (other configurations, "
+                         "baselines and per-kernel figures live in vi_normflows_amd/bench/), so "
+                         "today --full runs what a plain run does")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def _free_port() -> int:
@@ -156,6 +169,8 @@ def main() -> int:
     # leaves diverged replicas, whose step time must not be reported as a result.
     max_diff = _replica_max_diff(eng.params.master, world)
     identical = max_diff == 0.0
+    if a.dump_outputs and info.is_main:
+        _dump_outputs(eng, a.dump_outputs)
     buckets = runner.reducer.describe() if runner.reducer is not None else []
     loss = float(eng.loss.item())
     steps_done = int(eng.step_t.item())
@@ -215,6 +230,46 @@ def main() -> int:
         sys.stderr.write(f"bench.py: replicas diverged (max |master - master_rank0| = {max_diff})\n")
         return 3
     return 0
+
+
+DUMP_ROWS = 4096        # z_K rows kept (of --batch)
+DUMP_PARAMS = 1 << 22   # parameter / gradient elements kept (of 72.2 M at the defaults)
+
+
+def _dump_outputs(eng, out_dir: str) -> None:
+    """What the last timed step left for its caller, as float32 ``<name>.npy`` files: the free
+    energy, its per-sample terms, the flow's output samples z_K, the gradient and the updated
+    fp32 master parameters. z_K, the gradient and the parameters are fixed seeded samples (the
+    same rows / elements in every run with the same sizes): 46 MB in all at the defaults. The
+    engine's seed fixes the initial weights and the Philox noise of every step, so two runs with
+    the same arguments write the same arrays up to the order of floating-point atomics."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator().manual_seed(20240229)
+    A, Bh, _, _ = eng.zK_halves()
+    rows = torch.arange(eng.B)
+    if eng.B > DUMP_ROWS:
+        rows = torch.randperm(eng.B, generator=g)[:DUMP_ROWS].sort().values
+    P = eng.params
+    n = P.master.numel()
+    elems = torch.arange(n)
+    if n > DUMP_PARAMS:
+        elems = torch.randint(0, n, (DUMP_PARAMS,), generator=g).sort().values
+    rows_d, elems_d = rows.to(eng.device), elems.to(eng.device)
+    arrays = {
+        "free_energy": eng.loss.reshape(1),
+        "free_energy_per_sample": eng.frow,
+        "logp": eng.logp,
+        "logq0": eng.logq0,
+        "logdet": eng.ldj,
+        "zK": torch.cat([A.index_select(0, rows_d), Bh.index_select(0, rows_d)], 1),
+        "grad": P.grad.index_select(0, elems_d),
+        "params": P.master.index_select(0, elems_d),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def _replica_max_diff(master, world: int) -> float:

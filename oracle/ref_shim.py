@@ -1,6 +1,6 @@
-"""Load the reference's Python sources for parity tests.
+"""Load the reference's Python sources to record parity fixtures (``make_golden.py``).
 
-``autograd`` is not installed (no network), so a NumPy shim stands in for
+``autograd`` need not be installed: a NumPy shim stands in for
 ``autograd.numpy`` / ``autograd.scipy`` (the reference only uses them as NumPy).
 The reference package is imported under the name ``ref_normflows`` so it never
 collides with this repository's ``normflows`` compatibility shim.
@@ -43,7 +43,7 @@ def _install_autograd_shim():
 
 
 def load_reference(root):
-    """Import /root/reference/normflows/normflows as package ``ref_normflows``."""
+    """Import ``<root>/normflows/normflows`` as package ``ref_normflows``."""
     _install_autograd_shim()
     if "ref_normflows" in sys.modules:
         return sys.modules["ref_normflows"]

@@ -1,4 +1,3 @@
-import os
 import sys
 from pathlib import Path
 
@@ -7,7 +6,7 @@ import torch
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
-REFERENCE = Path(os.environ.get("VINF_REFERENCE", "/root/reference"))
+GOLDEN = ROOT / "tests" / "golden"
 
 
 def pytest_configure(config):
@@ -24,10 +23,23 @@ def pytest_collection_modifyitems(config, items):
 
 
 @pytest.fixture
-def reference_dir():
-    if not REFERENCE.exists():
-        pytest.skip("reference checkout not mounted")
-    return REFERENCE
+def golden_dir():
+    """Data files of the reference project (CSV, shipped checkpoints, result logs), stored with
+    the tests; ``oracle/make_golden.py`` writes them."""
+    return GOLDEN
+
+
+@pytest.fixture(scope="session")
+def ref_out():
+    """What the reference's own functions return on the tests' seeded inputs
+    (``oracle/make_golden.py``), read-only."""
+    import numpy as np
+
+    with np.load(GOLDEN / "reference_outputs.npz") as d:
+        out = {k: d[k] for k in d.files}
+    for v in out.values():
+        v.setflags(write=False)
+    return out
 
 
 @pytest.fixture

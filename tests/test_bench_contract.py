@@ -57,6 +57,37 @@ def test_bench_single_process_cpu():
     _check(recs[0], 1)
 
 
+def test_bench_dump_outputs_and_full_cpu(tmp_path):
+    """``--dump-outputs DIR`` writes the last timed step's results as float32 ``.npy`` files,
+    the same from run to run (same seeded weights and noise); ``--full`` is accepted and keeps
+    the result line's contract."""
+    import numpy as np
+
+    dumps = []
+    for tag, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / tag
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL,
+                            "--dump-outputs", str(d), *extra], cwd=ROOT, env=_env(),
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        recs = _json_lines(r.stdout)
+        assert len(recs) == 1
+        _check(recs[0], 1)
+        dumps.append({p.stem: np.load(p) for p in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert set(a) == set(b) == {"free_energy", "free_energy_per_sample", "logp", "logq0", "logdet",
+                                "zK", "grad", "params"}
+    assert a["zK"].shape == (64, 64) and a["free_energy_per_sample"].shape == (64,)
+    assert a["grad"].shape == a["params"].shape and a["grad"].size > 0
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        assert np.array_equal(a[k], b[k]), k
+    # the free energy is the fp32 mean of its 64 per-sample terms
+    fe, rows = float(a["free_energy"][0]), a["free_energy_per_sample"].astype(np.float64)
+    assert abs(fe - rows.mean()) <= 1e-5 * np.abs(rows).mean()
+    assert np.abs(a["grad"]).max() > 0
+
+
 def test_bench_torchrun_two_ranks_cpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()),

@@ -46,15 +46,15 @@ def test_latent_models(tmp_path):
     assert math.isfinite(s["free_energy"]) and abs(sum(s["weights"]) - 1) < 1e-5
 
 
-def test_bbvi_example(tmp_path, reference_dir):
+def test_bbvi_example(tmp_path, golden_dir):
     s = _run("bbvi_linreg", "--iters", "1500", "--out", str(tmp_path),
-             "--data", str(reference_dir / "data" / "HW0_data.csv"))
+             "--data", str(golden_dir / "data" / "HW0_data.csv"))
     assert abs(s["mu_post"][0] - 8.82) < 0.05 and abs(s["mu_vi"][0] - s["mu_post"][0]) < 0.05
 
 
-def test_mnist_examples(tmp_path, reference_dir):
-    s = _run("mnist_figures", "--models", str(reference_dir / "models" / "reg_mnist"),
-             "--results", str(reference_dir / "results" / "reg_free_energy2d.txt"), "--out", str(tmp_path / "f"))
+def test_mnist_examples(tmp_path, golden_dir):
+    s = _run("mnist_figures", "--models", str(golden_dir / "models" / "reg_mnist"),
+             "--results", str(golden_dir / "results" / "reg_free_energy2d.txt"), "--out", str(tmp_path / "f"))
     assert s["K"] == 8 and set(s["free_energy_vs_K"]) == {1, 2, 4, 8}
     assert (tmp_path / "f" / "latent_grid.png").exists()
     s = _run("learning_mnist", "--K", "2", "--dim-z", "2", "--iters", "20", "--n-data", "256",

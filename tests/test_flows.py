@@ -185,19 +185,19 @@ def test_flow_sequence_composition():
     _check_ldj(fs, D=3)
 
 
-def test_planar_matches_reference_source(reference_dir):
-    from ref_shim import ref_module
-
-    rf = ref_module(reference_dir, "flows")
+def test_planar_matches_reference_source(ref_out):
+    """Against the recorded results of the reference's ``flows.planar_flow``, ``_get_uhat`` and
+    ``m`` on these seeded inputs (``oracle/make_golden.py``)."""
     rng = np.random.RandomState(0)
     N, D = 7, 3
     z, w, u, b = rng.randn(N, D), rng.randn(N, D), rng.randn(N, D), rng.randn(N)
-    expect = rf.planar_flow(z, w, u, b)
+    expect = ref_out["planar_flow"]
+    assert expect.shape == (N, D)
     got = planar_flow(torch.tensor(z), torch.tensor(w), torch.tensor(u), torch.tensor(b),
                       variant="reference")
     assert np.allclose(got.numpy(), expect)
     # and the paper form differs (Q4)
     paper = planar_flow(torch.tensor(z), torch.tensor(w), torch.tensor(u), torch.tensor(b))
     assert not np.allclose(paper.numpy(), expect)
-    assert np.allclose(get_uhat(torch.tensor(u), torch.tensor(w)).numpy(), rf._get_uhat(u, w))
-    assert math.isclose(float(rf.m(0.3)), -1 + math.log(1 + math.exp(0.3)))
+    assert np.allclose(get_uhat(torch.tensor(u), torch.tensor(w)).numpy(), ref_out["planar_uhat"])
+    assert math.isclose(float(ref_out["planar_m_0p3"]), -1 + math.log(1 + math.exp(0.3)))

@@ -20,31 +20,31 @@ def _arch(Din, H, L, Dout, act, out_act=None):
     return a
 
 
-def test_feedforward_matches_reference_forward(reference_dir):
-    from ref_shim import ref_module
-
-    rnn = ref_module(reference_dir, "nn_models")
+def test_feedforward_matches_reference_forward(ref_out):
+    """Against the recorded results of the reference's ``nn_models.Feedforward`` on these seeded
+    inputs (``oracle/make_golden.py``)."""
     relu = lambda x: np.maximum(x, 0)  # noqa: E731
     arch = _arch(5, 7, 3, 4, relu)
-    ref = rnn.Feedforward(arch)
     ours = Feedforward(arch)
-    assert ours.D == ref.D == flat_size(5, 7, 3, 4)
+    assert ours.D == int(ref_out["ff_D"]) == flat_size(5, 7, 3, 4)
     rng = np.random.RandomState(0)
-    W = rng.randn(3, ref.D)
+    W = rng.randn(3, ours.D)
     x = rng.randn(5, 11)
-    assert np.allclose(ours.forward(W, x), ref.forward(W, x))
+    assert ours.forward(W, x).shape == ref_out["ff_forward"].shape
+    assert np.allclose(ours.forward(W, x), ref_out["ff_forward"])
     xs = rng.randn(3, 5, 11)
-    assert np.allclose(ours.forward(W, xs), ref.forward(W, xs))
+    assert ours.forward(W, xs).shape == ref_out["ff_forward_batched"].shape
+    assert np.allclose(ours.forward(W, xs), ref_out["ff_forward_batched"])
     # torch path and FlatMLP agree with the same flat vector
     m = FlatMLP(5, 7, 3, 4).double().load_flat(W[0])
     got = m(torch.tensor(x.T)).detach().numpy().T
-    assert np.allclose(got, ref.forward(W[:1], x)[0])
+    assert np.allclose(got, ref_out["ff_forward_first"])
     assert np.allclose(m.to_flat().numpy(), W[0])
 
 
-def test_shipped_checkpoints_load_with_reference_sizes(reference_dir):
-    files = sorted(glob.glob(str(reference_dir / "models" / "*" / "*.npy")))
-    assert files
+def test_shipped_checkpoints_load_with_reference_sizes(golden_dir):
+    files = sorted(glob.glob(str(golden_dir / "models" / "*" / "*.npy")))
+    assert len(files) == 14
     for f in files:
         w = load_flat(f)
         if "phi" in f:
@@ -55,40 +55,27 @@ def test_shipped_checkpoints_load_with_reference_sizes(reference_dir):
             assert w.size == 59472
 
 
-def test_vae_decodes_reference_checkpoint_like_reference(reference_dir):
+def test_vae_decodes_reference_checkpoint_like_reference(golden_dir, ref_out):
     """Our reference-compat VAE reproduces the reference pipeline (encode -> sample_from_pz with
-    the broadcast planar flow -> decode with sigmoid) on a shipped checkpoint."""
-    from ref_shim import ref_module
-
-    rnn = ref_module(reference_dir, "nn_models")
-    rflows = ref_module(reference_dir, "flows")
+    the broadcast planar flow -> decode with sigmoid) on a shipped checkpoint. The pipeline's
+    result (reference ``nn_models.Feedforward`` encoder and decoder around ``flows.planar_flow``,
+    eps = RandomState(0).randn(1, dz)) on the image below is recorded by
+    ``oracle/make_golden.py``."""
     K, dz = 2, 2
-    phi = load_flat(reference_dir / "models" / "reg_mnist" / f"weights_phi_{K}.npy")
-    theta = load_flat(reference_dir / "models" / "reg_mnist" / f"weights_theta_{K}.npy")
-    relu = lambda x: np.maximum(x, 0)  # noqa: E731
-    sig = lambda x: 1 / (1 + np.exp(-x))  # noqa: E731
-    enc = rnn.Feedforward(_arch(784, 64, 3, 2 * dz + 2 * dz * K + K, relu))
-    dec = rnn.Feedforward(_arch(dz, 64, 3, 784, relu, sig))
     x = synthetic_binary_images(1, seed=3).numpy().astype(np.float64)
-    P = enc.forward(phi.reshape(1, -1), x.T)[0]
-    mu0, lsd = P[:dz].reshape(1, dz), P[dz:2 * dz].reshape(1, dz)
-    W = P[2 * dz:2 * dz + K * dz].reshape(K, 1, dz)
-    U = P[2 * dz + K * dz:2 * dz + 2 * K * dz].reshape(K, 1, dz)
-    b = P[-K:].reshape(K, 1)
+    assert np.array_equal(x, ref_out["vae_x"])   # the image the recorded result was computed on
     eps = np.random.RandomState(0).randn(1, dz)
-    z = eps * np.sqrt(1e-7 + np.exp(lsd)) + mu0
-    for k in range(K):
-        z = rflows.planar_flow(z, W[k], U[k], b[k])
-    ref_probs = dec.forward(theta.reshape(1, -1), z.T)[0].T
+    ref_probs = ref_out["vae_probs"]
 
     vae = PlanarVAE(VAEConfig(dim_z=dz, K=K, flow_variant="reference", encode_layout="reference"))
-    vae.load_reference(reference_dir / "models" / "reg_mnist" / f"weights_phi_{K}.npy",
-                       reference_dir / "models" / "reg_mnist" / f"weights_theta_{K}.npy")
+    vae.load_reference(golden_dir / "models" / "reg_mnist" / f"weights_phi_{K}.npy",
+                       golden_dir / "models" / "reg_mnist" / f"weights_theta_{K}.npy")
     xt = torch.tensor(x)
     m, lv, (Wt, Ut, bt) = vae.encode(xt)
     zt = torch.tensor(eps) * torch.sqrt(1e-7 + torch.exp(lv)) + m
     zt, _ = vae.flow(zt, (Wt, Ut, bt))
     probs = vae.decode_probs(zt).detach().numpy()
+    assert probs.shape == ref_probs.shape
     assert np.allclose(probs, ref_probs, atol=1e-10)
 
 
@@ -133,12 +120,12 @@ def test_make_batch_iter_semantics():
     assert torch.equal(it(5), it(5))                                # deterministic in t
 
 
-def test_free_energy_logs_parse(reference_dir, tmp_path):
-    fe = parse_free_energy(reference_dir / "results" / "free_energy.txt")
+def test_free_energy_logs_parse(golden_dir, tmp_path):
+    fe = parse_free_energy(golden_dir / "results" / "free_energy.txt")
     assert fe == pytest.approx({1: 15992.437053233414, 2: 15630.388433090544,
                                 4: 15148.111370199504, 8: 22943.708525957405,
                                 16: 24660.819476614})
-    fe2 = parse_free_energy(reference_dir / "results" / "free_energy2d.txt")
+    fe2 = parse_free_energy(golden_dir / "results" / "free_energy2d.txt")
     assert set(fe2) == {1, 2, 8}   # last line glues two records (reference quirk)
     p = tmp_path / "fe.txt"
     append_free_energy(p, 4, -1.5)
