@@ -18,6 +18,17 @@ void nf_launch_coupling_bwd(const void* s, int s_is_shat_bf16, long ld_s, const 
                             long ld_gx, int B, int Dh, float scale, int gx_accumulate,
                             int dst_pad_to, hipStream_t stream);
 
+// spline.hip: rational-quadratic spline coupling transform. params [B, (3K-1) Dh] plane-major
+// (fp32 or bf16), x / y / g_out / gx [B, Dh] fp32 contiguous, ldj / g_ldj [B]; 2 <= K <= 32.
+// x is the input of the direction taken (the inverse reads y there), in the backward too.
+void nf_launch_rqs_fwd(const void* params, int params_is_bf16, const float* x, float* y,
+                       float* ldj, int B, int Dh, int K, float bound, int inverse, int ldj_init,
+                       hipStream_t stream);
+// dparams in the dtype of params, every column written
+void nf_launch_rqs_bwd(const void* params, int params_is_bf16, const float* x, const float* g_out,
+                       const float* g_ldj, void* dparams, float* gx, int B, int Dh, int K,
+                       float bound, int inverse, hipStream_t stream);
+
 // elbo.hip
 void nf_launch_target_logp_grad(int kind, const float* A, long lda, const float* Bh, long ldb,
                                 float* gA, long ldga, float* gB, long ldgb, int grad_accumulate,

@@ -44,6 +44,11 @@ def build_flow(kind: str, dim: int, K: int, **kw):
         from ..flows.coupling import RealNVP
 
         return RealNVP(dim, n_layers=K, hidden=kw.get("hidden", 64), n_hidden=2)
+    if kind == "nsf":
+        from ..flows.spline import NeuralSplineFlow
+
+        return NeuralSplineFlow(dim, n_layers=K, hidden=kw.get("hidden", 64),
+                                bins=kw.get("bins", 8), bound=kw.get("bound", 4.0))
     if kind == "iaf":
         from ..flows.base import Reverse
         from ..flows.made import IAF

@@ -206,3 +206,75 @@ def maf_bwd(gu, u, o, bound, c_ldj, dout, gx):
     gx.copy_(gu * ea)
     dout[:, :D].copy_((-gu * ea).to(dout.dtype))
     dout[:, D:2 * D].copy_(((c_ldj - gu * u) * (1 - t * t)).to(dout.dtype))
+
+
+# ------------------------------------------- rational-quadratic spline (spline.hip oracle)
+RQS_MIN = 1e-3                                   # min_w = min_h = min_d
+RQS_C0 = math.log(math.expm1(1.0 - RQS_MIN))     # softplus(RQS_C0) + RQS_MIN == 1
+
+
+def rqs_knots(params, K: int, bound: float):
+    """Knots of the monotone rational-quadratic spline (Durkan et al. 2019) from the plane-major
+    conditioner output ``params`` [B, (3K-1) Dh]: planes 0..K-1 unnormalised widths, K..2K-1
+    heights, 2K..3K-2 interior derivatives. Returns ``xk, w, yk, h, d`` with knots / derivatives
+    [B, K+1, Dh] and bin sizes [B, K, Dh]; the end knots are exactly -+bound, the end
+    derivatives exactly 1 (linear tails), and all-zero params give the identity spline."""
+    B = params.shape[0]
+    if not 2 <= K <= 32 or K * RQS_MIN >= 1.0:
+        raise ValueError(f"rqs: need 2 <= K <= 32, got {K}")
+    if not bound > 0:
+        raise ValueError(f"rqs: need bound > 0, got {bound}")
+    if params.shape[1] % (3 * K - 1):
+        raise ValueError(f"rqs: params width {params.shape[1]} is no multiple of 3K-1")
+    p = params.reshape(B, 3 * K - 1, -1)
+    lo = p.new_full((B, 1, p.shape[2]), -bound)
+    one = torch.ones_like(lo)
+
+    def bins(u):
+        sz = 2.0 * bound * (RQS_MIN + (1.0 - K * RQS_MIN) * torch.softmax(u, 1))
+        kn = torch.cat([lo, lo + torch.cumsum(sz, 1)[:, :-1], -lo], 1)
+        return kn, sz
+
+    xk, w = bins(p[:, :K])
+    yk, h = bins(p[:, K:2 * K])
+    d = torch.cat([one, RQS_MIN + torch.nn.functional.softplus(p[:, 2 * K:] + RQS_C0), one], 1)
+    return xk, w, yk, h, d
+
+
+def rqs_transform(params, x, K: int, bound: float, inverse: bool = False):
+    """Differentiable element-wise RQ-spline transform of ``x`` [B, Dh] in the dtype of ``x``;
+    returns ``(y, ldj)`` with ``ldj`` [B] the summed log-derivative of the direction taken.
+    Outside (-bound, bound) it is the identity with log-derivative 0."""
+    params = params.to(x.dtype)
+    xk, w, yk, h, d = rqs_knots(params, K, bound)
+    inside = (x > -bound) & (x < bound)
+    v = x.clamp(-bound, bound)
+    kn = yk if inverse else xk
+    k = (v.unsqueeze(1) >= kn[:, 1:K]).sum(1, keepdim=True)     # interior knots <= v
+
+    def at(t, i):
+        return t.gather(1, i).squeeze(1)
+
+    bx, bw, by, bh = at(xk, k), at(w, k), at(yk, k), at(h, k)
+    d0, d1 = at(d, k), at(d, k + 1)
+    s = bh / bw
+    e = d1 + d0 - 2.0 * s
+    if inverse:
+        dl = v - by
+        a = bh * (s - d0) + dl * e
+        b = bh * d0 - dl * e
+        c = -s * dl
+        th = 2.0 * c / (-b - torch.sqrt((b * b - 4.0 * a * c).clamp_min(0.0)))
+        out = th * bw + bx
+    else:
+        th = (v - bx) / bw
+    t1 = th * (1.0 - th)
+    den = s + e * t1
+    if not inverse:
+        out = by + bh * (s * th * th + d0 * t1) / den
+    lg = (2.0 * torch.log(s) + torch.log(d1 * th * th + 2.0 * s * t1 + d0 * (1.0 - th) ** 2)
+          - 2.0 * torch.log(den))
+    if inverse:
+        lg = -lg
+    out = torch.where(inside, out, x)
+    return out, torch.where(inside, lg, torch.zeros_like(lg)).sum(1)

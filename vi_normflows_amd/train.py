@@ -69,9 +69,11 @@ def run_flow_vi(cfg, out, info, logger):
     from .viz.plots import plot_density_and_samples, plot_loss
 
     dev = _device(cfg, info)
+    # spline-flow options (flow=nsf), passed through only when set
+    flow_kw = {k: cfg.extra[k] for k in ("bins", "bound") if cfg.extra.get(k) is not None}
     r = fit_flow_vi(cfg.target, cfg.flow, cfg.K, cfg.iters, cfg.lr, cfg.batch, cfg.optimizer,
                     cfg.schedule, device=dev, seed=rank_seed(cfg.seed, info.rank),
-                    log_every=cfg.log_every, logger=logger, hidden=cfg.hidden)
+                    log_every=cfg.log_every, logger=logger, hidden=cfg.hidden, **flow_kw)
     if info.is_main:
         with torch.no_grad():
             zs = r.flow(r.base.sample(2000).to(dev))[0].cpu().double()
