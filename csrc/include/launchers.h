@@ -29,6 +29,28 @@ void nf_launch_rqs_bwd(const void* params, int params_is_bf16, const float* x, c
                        const float* g_ldj, void* dparams, float* gx, int B, int Dh, int K,
                        float bound, int inverse, hipStream_t stream);
 
+// sylvester.hip: fused K-layer Sylvester flow stack, fp32, 1 <= D <= 64, 0 <= H <= 16, K >= 1.
+// Every parameter (gradient) tensor is [rows, K, width] with a dense inner [K, width] block and a
+// row stride in elements (0 = shared); widths: R1 / R2 D(D-1)/2 (strict upper, packed by
+// column), d1 / d2 / b D, V H D. z / zK / gz / dz [N, D], ldj / gl [N], saved [N, K, D] dense;
+// flips: K host bytes (layer k reverses the coordinates).
+struct NfSylParams {
+  const float *R1, *R2, *d1, *d2, *b, *V;
+  long rs_R1, rs_R2, rs_d1, rs_d2, rs_b, rs_V;
+};
+struct NfSylGrads {
+  float *R1, *R2, *d1, *d2, *b, *V;
+  long rs_R1, rs_R2, rs_d1, rs_d2, rs_b, rs_V;
+};
+// saved may be null (no backward will follow)
+void nf_launch_sylvester_fwd(const float* z, const NfSylParams& p, const unsigned char* flips,
+                             float* zK, float* ldj, float* saved, int N, int D, int K, int H,
+                             hipStream_t stream);
+// per-row gradients, every entry written
+void nf_launch_sylvester_bwd(const float* saved, const NfSylParams& p, const unsigned char* flips,
+                             const float* gz, const float* gl, float* dz, const NfSylGrads& g,
+                             int N, int D, int K, int H, hipStream_t stream);
+
 // elbo.hip
 void nf_launch_target_logp_grad(int kind, const float* A, long lda, const float* Bh, long ldb,
                                 float* gA, long ldga, float* gB, long ldgb, int grad_accumulate,

@@ -2,4 +2,5 @@
 from vi_normflows_amd.compat.reference_api import _get_uhat, m, planar_flow  # noqa: F401
 from vi_normflows_amd.flows import (IAF, MAF, MADE, AffineCoupling, DiagAffine,  # noqa: F401
                                     FlowSequence, Planar, PlanarStack, Radial, RadialStack,
-                                    RealNVP, RQSCoupling, NeuralSplineFlow)
+                                    RealNVP, RQSCoupling, NeuralSplineFlow,
+                                    SylvesterStack, AmortizedSylvester)

@@ -1,5 +1,5 @@
 """Normalizing-flow layers: planar, radial, diagonal affine, RealNVP coupling, MADE/IAF/MAF,
-rational-quadratic spline coupling."""
+rational-quadratic spline coupling, Sylvester."""
 from .affine import DiagAffine
 from .base import Flow, FlowDistribution, FlowSequence, Permute, Reverse
 from .coupling import AffineCoupling, RealNVP, coupling_transform
@@ -9,6 +9,7 @@ from .planar import (AmortizedPlanar, Planar, PlanarStack, get_uhat, m, planar_f
 from .radial import (AmortizedRadial, Radial, RadialStack, radial_params, radial_stack,
                      radial_stack_reference)
 from .spline import NeuralSplineFlow, RQSCoupling
+from .sylvester import AmortizedSylvester, SylvesterStack
 
 __all__ = [
     "Flow", "FlowSequence", "FlowDistribution", "Permute", "Reverse", "DiagAffine",
@@ -16,5 +17,5 @@ __all__ = [
     "made_degrees", "made_masks", "Planar", "PlanarStack", "AmortizedPlanar", "get_uhat", "m",
     "planar_flow", "planar_stack", "planar_stack_reference", "Radial", "RadialStack",
     "AmortizedRadial", "radial_params", "radial_stack", "radial_stack_reference",
-    "RQSCoupling", "NeuralSplineFlow",
+    "RQSCoupling", "NeuralSplineFlow", "SylvesterStack", "AmortizedSylvester",
 ]

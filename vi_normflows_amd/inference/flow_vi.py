@@ -49,6 +49,11 @@ def build_flow(kind: str, dim: int, K: int, **kw):
 
         return NeuralSplineFlow(dim, n_layers=K, hidden=kw.get("hidden", 64),
                                 bins=kw.get("bins", 8), bound=kw.get("bound", 4.0))
+    if kind == "sylvester":
+        from ..flows.sylvester import SylvesterStack
+
+        return SylvesterStack(dim, K, householders=kw.get("householders", 1),
+                              basis=kw.get("basis", "householder"))
     if kind == "iaf":
         from ..flows.base import Reverse
         from ..flows.made import IAF

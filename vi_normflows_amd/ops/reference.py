@@ -278,3 +278,94 @@ def rqs_transform(params, x, K: int, bound: float, inverse: bool = False):
         lg = -lg
     out = torch.where(inside, out, x)
     return out, torch.where(inside, lg, torch.zeros_like(lg)).sum(1)
+
+
+# ------------------------------------------------- Sylvester flow stack (sylvester.hip oracle)
+SYL_EPS = 1e-7        # log(|psi| + eps): the guard of the planar stack
+SYL_VV_MIN = 1e-20    # v.v is clamped from below: v = 0 is the identity reflection
+
+
+def tri_index(D: int, device=None):
+    """Rows and columns of the strict upper part of a D x D matrix in packed order: by column,
+    entry (i, j) with i < j at index j (j - 1) / 2 + i."""
+    cols = torch.repeat_interleave(torch.arange(D, device=device), torch.arange(D, device=device))
+    rows = torch.arange(D * (D - 1) // 2, device=device) - cols * (cols - 1) // 2
+    return rows, cols
+
+
+def tri_pack(R):
+    """[..., D, D] -> [..., D (D - 1) / 2]: the strict upper part, packed by column."""
+    rows, cols = tri_index(R.shape[-1], R.device)
+    return R[..., rows, cols]
+
+
+def tri_unpack(Rp, D: int):
+    """[..., D (D - 1) / 2] -> [..., D, D] strictly upper triangular (differentiable)."""
+    if Rp.shape[-1] != D * (D - 1) // 2:
+        raise ValueError(f"tri_unpack: {Rp.shape[-1]} packed entries, D = {D} needs "
+                         f"{D * (D - 1) // 2}")
+    rows, cols = tri_index(D, Rp.device)
+    out = Rp.new_zeros(*Rp.shape[:-1], D, D)
+    out[..., rows, cols] = Rp
+    return out
+
+
+def householder(x, v):
+    """H_v x = x - 2 v (v.x) / max(v.v, 1e-20) over the last dim; v [D] or [N, D]."""
+    n = (v * v).sum(-1, keepdim=True).clamp_min(SYL_VV_MIN)
+    return x - 2.0 * v * ((v * x).sum(-1, keepdim=True) / n)
+
+
+def sylvester_basis_apply(x, Vk, flip: bool, transpose: bool):
+    """Q x (``transpose=False``) or Q^T x for Q = P^flip H_1 ... H_H; x [N, D], Vk [H, D] or
+    [N, H, D], P the coordinate reversal."""
+    H = Vk.shape[-2]
+    if transpose:
+        if flip:
+            x = x.flip(-1)
+        for h in range(H):
+            x = householder(x, Vk[..., h, :])
+        return x
+    for h in reversed(range(H)):
+        x = householder(x, Vk[..., h, :])
+    return x.flip(-1) if flip else x
+
+
+def sylvester_stack_reference(z, R1, R2, d1, d2, b, V, flips):
+    """Composite K-layer Sylvester flow stack (van den Berg et al. 2018) with M = D, in the dtype
+    of ``z`` and differentiable in every tensor argument. Per layer k:
+
+        t  = Q^T z,  Q = P^flip_k H_1 ... H_H     (Householder reflections of V[k], reversal P)
+        h  = tanh(d2 * t + R2 t + b)
+        z' = z + Q (d1 * h + R1 h)
+        ldj += sum_i log(|1 + (1 - h_i^2) d1_i d2_i| + 1e-7)
+
+    ``R1`` / ``R2`` are strictly upper triangular, packed by column ([.., D (D - 1) / 2],
+    :func:`tri_pack`); ``d1`` / ``d2`` are the already squashed diagonals. Each parameter is
+    shared ([K, ...]) or per-sample ([N, K, ...]); ``V`` is [.., K, H, D] (H may be 0);
+    ``flips`` holds K truth values. Returns ``(z_K, ldj[N])``.
+    """
+    N, D = z.shape
+    K = d1.shape[-2]
+    if len(flips) != K:
+        raise ValueError(f"sylvester: {len(flips)} flips for K = {K} layers")
+
+    def layer(t, k, shared_dim):
+        return t[k] if t.dim() == shared_dim else t[:, k]
+
+    def mv(A, x):   # A [D, D] or [N, D, D], x [N, D]
+        return x @ A.t() if A.dim() == 2 else torch.einsum("nij,nj->ni", A, x)
+
+    ld = torch.zeros(N, dtype=z.dtype, device=z.device)
+    for k in range(K):
+        A1 = tri_unpack(layer(R1, k, 2), D)
+        A2 = tri_unpack(layer(R2, k, 2), D)
+        e1, e2, bk = layer(d1, k, 2), layer(d2, k, 2), layer(b, k, 2)
+        Vk = layer(V, k, 3)
+        flip = bool(flips[k])
+        t = sylvester_basis_apply(z, Vk, flip, transpose=True)
+        h = torch.tanh(e2 * t + mv(A2, t) + bk)
+        y = e1 * h + mv(A1, h)
+        z = z + sylvester_basis_apply(y, Vk, flip, transpose=False)
+        ld = ld + torch.log(torch.abs(1.0 + (1.0 - h * h) * e1 * e2) + SYL_EPS).sum(-1)
+    return z, ld

@@ -69,8 +69,9 @@ def run_flow_vi(cfg, out, info, logger):
     from .viz.plots import plot_density_and_samples, plot_loss
 
     dev = _device(cfg, info)
-    # spline-flow options (flow=nsf), passed through only when set
-    flow_kw = {k: cfg.extra[k] for k in ("bins", "bound") if cfg.extra.get(k) is not None}
+    # spline-flow (flow=nsf) and Sylvester (flow=sylvester) options, passed through only when set
+    flow_kw = {k: cfg.extra[k] for k in ("bins", "bound", "householders", "basis")
+               if cfg.extra.get(k) is not None}
     r = fit_flow_vi(cfg.target, cfg.flow, cfg.K, cfg.iters, cfg.lr, cfg.batch, cfg.optimizer,
                     cfg.schedule, device=dev, seed=rank_seed(cfg.seed, info.rank),
                     log_every=cfg.log_every, logger=logger, hidden=cfg.hidden, **flow_kw)
@@ -161,7 +162,14 @@ def run_planar_vae(cfg, out, info, logger):
         X = synthetic_binary_images(cfg.extra.get("n_data", 2000), cfg.dim, seed=cfg.seed)
     vcfg = VAEConfig(dim_x=cfg.dim, dim_z=cfg.dim_z, K=cfg.K, width=cfg.hidden,
                      hidden_layers=cfg.n_hidden)
-    vae = PlanarVAE(vcfg)
+    sylvester = cfg.extra.get("flow") == "sylvester"
+    if sylvester:   # Sylvester layers in place of the planar ones: module path only
+        from .models.sylvester_vae import SylvesterVAE
+
+        vae = SylvesterVAE(vcfg, householders=int(cfg.extra.get("householders", 1)),
+                           basis=cfg.extra.get("basis", "householder"))
+    else:
+        vae = PlanarVAE(vcfg)
     vae.init_reference(generator=torch.Generator().manual_seed(cfg.seed))
     vae.to(dev)
     it = make_batch_iter(X, cfg.batch, cfg.iters, generator=g, rank=info.rank, world=info.world)
@@ -171,7 +179,8 @@ def run_planar_vae(cfg, out, info, logger):
     # CPU: only on request (extra.engine="force": the engine's autograd reference step, e.g.
     # the gloo DP tests of the engine's runner contract)
     want = cfg.extra.get("engine", True)
-    engine_ok = (cfg.optimizer in ENGINE_OPTIMIZERS and cfg.schedule in ("none", "reference")
+    engine_ok = (not sylvester and cfg.optimizer in ENGINE_OPTIMIZERS
+                 and cfg.schedule in ("none", "reference")
                  and ((dev.type == "cuda" and want is not False and PlanarVAEEngine.supported(vcfg))
                       or (dev.type != "cuda" and want == "force" and cfg.hidden == 64)))
     if engine_ok:
