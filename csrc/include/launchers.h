@@ -29,6 +29,18 @@ void nf_launch_rqs_bwd(const void* params, int params_is_bf16, const float* x, c
                        const float* g_ldj, void* dparams, float* gx, int B, int Dh, int K,
                        float bound, int inverse, hipStream_t stream);
 
+// dsf.hip: deep sigmoidal flow transformer. params [B, 3H D] plane-major (fp32 or bf16; planes
+// ua, b, uw), x / y / g_out / gx [B, D] fp32 contiguous, ldj / g_ldj [B]; 1 <= H <= 32.
+// The forward's x is the input of the direction taken (the inverse reads y there); the
+// backward's x is the x-side value in both directions (the inverse's output).
+void nf_launch_dsf_fwd(const void* params, int params_is_bf16, const float* x, float* y,
+                       float* ldj, int B, int D, int H, int inverse, int ldj_init,
+                       hipStream_t stream);
+// dparams in the dtype of params, every column written
+void nf_launch_dsf_bwd(const void* params, int params_is_bf16, const float* x, const float* g_out,
+                       const float* g_ldj, void* dparams, float* gx, int B, int D, int H,
+                       int inverse, hipStream_t stream);
+
 // sylvester.hip: fused K-layer Sylvester flow stack, fp32, 1 <= D <= 64, 0 <= H <= 16, K >= 1.
 // Every parameter (gradient) tensor is [rows, K, width] with a dense inner [K, width] block and a
 // row stride in elements (0 = shared); widths: R1 / R2 D(D-1)/2 (strict upper, packed by

@@ -3,4 +3,5 @@ from vi_normflows_amd.compat.reference_api import _get_uhat, m, planar_flow  # n
 from vi_normflows_amd.flows import (IAF, MAF, MADE, AffineCoupling, DiagAffine,  # noqa: F401
                                     FlowSequence, Planar, PlanarStack, Radial, RadialStack,
                                     RealNVP, RQSCoupling, NeuralSplineFlow,
-                                    SylvesterStack, AmortizedSylvester)
+                                    SylvesterStack, AmortizedSylvester, DSFCoupling,
+                                    DSFAutoregressive, NeuralAutoregressiveFlow)

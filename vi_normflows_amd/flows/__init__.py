@@ -1,9 +1,10 @@
 """Normalizing-flow layers: planar, radial, diagonal affine, RealNVP coupling, MADE/IAF/MAF,
-rational-quadratic spline coupling, Sylvester."""
+rational-quadratic spline coupling, Sylvester, neural autoregressive (deep sigmoidal)."""
 from .affine import DiagAffine
 from .base import Flow, FlowDistribution, FlowSequence, Permute, Reverse
 from .coupling import AffineCoupling, RealNVP, coupling_transform
 from .made import IAF, MADE, MAF, MaskedLinear, made_degrees, made_masks
+from .naf import DSFAutoregressive, DSFCoupling, NeuralAutoregressiveFlow
 from .planar import (AmortizedPlanar, Planar, PlanarStack, get_uhat, m, planar_flow,
                      planar_stack, planar_stack_reference)
 from .radial import (AmortizedRadial, Radial, RadialStack, radial_params, radial_stack,
@@ -18,4 +19,5 @@ __all__ = [
     "planar_flow", "planar_stack", "planar_stack_reference", "Radial", "RadialStack",
     "AmortizedRadial", "radial_params", "radial_stack", "radial_stack_reference",
     "RQSCoupling", "NeuralSplineFlow", "SylvesterStack", "AmortizedSylvester",
+    "DSFCoupling", "DSFAutoregressive", "NeuralAutoregressiveFlow",
 ]

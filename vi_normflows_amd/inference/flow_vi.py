@@ -54,6 +54,12 @@ def build_flow(kind: str, dim: int, K: int, **kw):
 
         return SylvesterStack(dim, K, householders=kw.get("householders", 1),
                               basis=kw.get("basis", "householder"))
+    if kind == "naf":
+        from ..flows.naf import NeuralAutoregressiveFlow
+
+        return NeuralAutoregressiveFlow(dim, n_layers=K, units=kw.get("units", 8),
+                                        hidden=kw.get("hidden", 64),
+                                        conditioner=kw.get("conditioner", "made"))
     if kind == "iaf":
         from ..flows.base import Reverse
         from ..flows.made import IAF

@@ -18,7 +18,9 @@ autograd node:
 For an IAF layer (``iaf_gated``) the gated update ``y = m + sigmoid(s + b)(z - m)`` and its
 log-det run in ``csrc/kernels/maf.hip`` (``iaf_gate_fwd/bwd``) straight on the MADE's bf16
 output; its backward writes the bf16 ``[dm | ds]`` operand of the masked GEMMs and the direct
-``dz`` path, onto which the input-gradient GEMM accumulates the MADE path.
+``dz`` path, onto which the input-gradient GEMM accumulates the MADE path. MAF's density
+direction (``maf_inverse``) and the MADE-conditioned deep sigmoidal flow layer
+(``dsf_autoregressive``, ``csrc/kernels/dsf.hip``) are built the same way.
 
 Reference parity: the IAF VAE of ``SURVEY.md`` config 4 (the reference's planar-flow VAE
 ``src/learning_mnist.py`` with IAF layers, Kingma et al. 2016); numerics are pinned against the
@@ -288,3 +290,44 @@ def maf_inverse(maf, x, context=None):
     has_ctx = made.ctx is not None and context is not None
     return _MAFInverseFn.apply(made, maf.bound, x.contiguous(), context if has_ctx else None,
                                *_params(made, has_ctx))
+
+
+class _DSFAutoregressiveFn(torch.autograd.Function):
+    """MADE-conditioned deep sigmoidal flow layer (``flows.naf.DSFAutoregressive.forward``): the
+    fused MADE, then ``dsf_fwd`` straight on its bf16 plane-major [N, 3 units D] output and,
+    backward, ``dsf_bwd`` writing the bf16 operand of the masked GEMMs and the direct ``dz``
+    path (csrc/kernels/dsf.hip)."""
+
+    @staticmethod
+    def forward(ctx, made, units, z, context, *params):
+        from .dsf import dsf_fwd
+
+        o, saved = _made_fwd(made, z, context)
+        y, ldj = dsf_fwd(o, z, units)
+        ctx.made, ctx.saved, ctx.units = made, saved, units
+        ctx.save_for_backward(z, o)
+        return y, ldj
+
+    @staticmethod
+    def backward(ctx, gy, gldj):
+        from .dsf import dsf_bwd
+
+        z, o = ctx.saved_tensors
+        if gy is None:
+            gy = torch.zeros_like(z)
+        gl = gldj if gldj is not None else torch.zeros(z.shape[0], device=z.device)
+        dout, gz = dsf_bwd(o, z, gy.float().contiguous(), gl.float().contiguous(), ctx.units)
+        need = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        dz, dctx, grads = _made_bwd(ctx.made, ctx.saved, dout, gz, need)
+        if not need:
+            dz = None
+        ctx.saved = None
+        return (None, None, dz, dctx, *grads)
+
+
+def dsf_autoregressive(layer, z, context=None):
+    """(y, ldj) of a MADE-conditioned DSF layer through the fused path."""
+    made = layer.made
+    has_ctx = made.ctx is not None and context is not None
+    return _DSFAutoregressiveFn.apply(made, layer.units, z.contiguous(),
+                                      context if has_ctx else None, *_params(made, has_ctx))

@@ -280,6 +280,70 @@ def rqs_transform(params, x, K: int, bound: float, inverse: bool = False):
     return out, torch.where(inside, lg, torch.zeros_like(lg)).sum(1)
 
 
+# ------------------------------------------------------ deep sigmoidal flow (dsf.hip oracle)
+DSF_C0 = math.log(math.e - 1.0)     # softplus(DSF_C0) == 1
+DSF_BISECT = 64                     # halvings of the inverse's bracket
+
+
+def dsf_units(params, H: int):
+    """Units of the deep sigmoidal flow (Huang et al. 2018) from the plane-major conditioner
+    output ``params`` [B, 3H D]: planes 0..H-1 raw slopes, H..2H-1 shifts, 2H..3H-1 mixture
+    logits. Returns ``a, b, logw`` [B, H, D] with a = softplus(ua + c0) > 0 and
+    logw = log softmax(uw); all-zero params give a = 1, b = 0, w = 1/H: the identity."""
+    if not 1 <= H <= 32:
+        raise ValueError(f"dsf: need 1 <= H <= 32, got {H}")
+    if params.dim() != 2 or params.shape[1] % (3 * H):
+        raise ValueError(f"dsf: params width {tuple(params.shape)} is no multiple of 3H")
+    p = params.reshape(params.shape[0], 3 * H, -1)
+    a = torch.nn.functional.softplus(p[:, :H] + DSF_C0)
+    return a, p[:, H:2 * H], torch.log_softmax(p[:, 2 * H:], 1)
+
+
+def _dsf_lse(t):
+    """logsumexp over the units (dim 1) of [B, H, D]. The shift carries no gradient; written out
+    because torch.logsumexp is slow over a short strided dimension on the CPU."""
+    m = torch.nan_to_num(t.detach().amax(1, keepdim=True), nan=0.0, posinf=0.0, neginf=0.0)
+    return torch.log(torch.exp(t - m).sum(1)) + m.squeeze(1)
+
+
+def _dsf_eval(a, b, logw, x):
+    """y = logit(sum_h w_h sigmoid(a_h x + b_h)) and log dy/dx, element-wise [B, D], in log
+    space: nothing overflows and no mixture term is lost for large |x| or spread logits."""
+    pj = a * x.unsqueeze(1) + b
+    lsp = torch.nn.functional.logsigmoid(pj)
+    lsn = torch.nn.functional.logsigmoid(-pj)
+    logs = _dsf_lse(logw + lsp)
+    log1ms = _dsf_lse(logw + lsn)       # sum w = 1
+    L = _dsf_lse(logw + torch.log(a) + lsp + lsn) - logs - log1ms
+    return logs - log1ms, L
+
+
+def dsf_transform(params, x, H: int, inverse: bool = False):
+    """Differentiable element-wise deep-sigmoidal-flow transform of ``x`` [B, D] in the dtype of
+    ``x``; returns ``(y, ldj)`` with ``ldj`` [B] the summed log-derivative of the direction taken.
+
+    The inverse has no closed form. y lies in [min_h p_h, max_h p_h], so the root lies in
+    [min_h (y - b_h) / a_h, max_h (y - b_h) / a_h]; that bracket is bisected without a graph and
+    one Newton step with a detached slope, x = x* - (f(x*, p) - y) / f'(x*), re-attaches it, so
+    autograd gives the implicit-function gradients for ``params`` and ``y``; ldj = -L(x, p)."""
+    a, b, logw = dsf_units(params.to(x.dtype), H)
+    if not inverse:
+        y, L = _dsf_eval(a, b, logw, x)
+        return y, L.sum(1)
+    with torch.no_grad():
+        r = (x.unsqueeze(1) - b) / a
+        lo, hi = r.amin(1), r.amax(1)
+        for _ in range(DSF_BISECT):
+            mid = 0.5 * lo + 0.5 * hi
+            below = _dsf_eval(a, b, logw, mid)[0] < x
+            lo = torch.where(below, mid, lo)
+            hi = torch.where(below, hi, mid)
+        xs = 0.5 * lo + 0.5 * hi
+    f, L = _dsf_eval(a, b, logw, xs)
+    out = xs - (f - x) / torch.exp(L).detach()
+    return out, -_dsf_eval(a, b, logw, out)[1].sum(1)
+
+
 # ------------------------------------------------- Sylvester flow stack (sylvester.hip oracle)
 SYL_EPS = 1e-7        # log(|psi| + eps): the guard of the planar stack
 SYL_VV_MIN = 1e-20    # v.v is clamped from below: v = 0 is the identity reflection

@@ -69,8 +69,10 @@ def run_flow_vi(cfg, out, info, logger):
     from .viz.plots import plot_density_and_samples, plot_loss
 
     dev = _device(cfg, info)
-    # spline-flow (flow=nsf) and Sylvester (flow=sylvester) options, passed through only when set
-    flow_kw = {k: cfg.extra[k] for k in ("bins", "bound", "householders", "basis")
+    # spline-flow (flow=nsf), Sylvester (flow=sylvester) and neural autoregressive (flow=naf)
+    # options, passed through only when set
+    flow_kw = {k: cfg.extra[k] for k in ("bins", "bound", "householders", "basis", "units",
+                                         "conditioner")
                if cfg.extra.get(k) is not None}
     r = fit_flow_vi(cfg.target, cfg.flow, cfg.K, cfg.iters, cfg.lr, cfg.batch, cfg.optimizer,
                     cfg.schedule, device=dev, seed=rank_seed(cfg.seed, info.rank),
