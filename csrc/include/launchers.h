@@ -271,6 +271,21 @@ void nf_launch_radial_fwd(const float* z, const float* Z0, const float* AL, cons
 void nf_launch_radial_bwd(const float* saved, const float* Z0, const float* AL, const float* BE,
                           const float* gz, const float* gl, float* dz, float* dZ0, float* dA,
                           float* dBe, int N, int D, int K, int per_sample, hipStream_t stream);
+// inverses of the paper-variant planar stack and of the radial stack: x from y, layers undone
+// K-1 .. 0, saved[k] = the preimage under layer k; the backwards write per-row gradients
+void nf_launch_planar_inv(const float* y, const float* W, const float* U, const float* B, float* x,
+                          float* ldj, float* saved, int N, int D, int K, int per_sample,
+                          hipStream_t stream);
+void nf_launch_planar_inv_bwd(const float* saved, const float* W, const float* U, const float* B,
+                              const float* gx, const float* gl, float* dy, float* dW, float* dU,
+                              float* dB, int N, int D, int K, int per_sample, hipStream_t stream);
+void nf_launch_radial_inv(const float* y, const float* Z0, const float* AL, const float* BE,
+                          float* x, float* ldj, float* saved, int N, int D, int K,
+                          int per_sample, hipStream_t stream);
+void nf_launch_radial_inv_bwd(const float* saved, const float* Z0, const float* AL,
+                              const float* BE, const float* gx, const float* gl, float* dy,
+                              float* dZ0, float* dA, float* dBe, int N, int D, int K,
+                              int per_sample, hipStream_t stream);
 
 // masked (MADE) GEMMs: per-N-tile K ranges [ntn][2] / per-tile skip flags [ntm*ntn] (128x128 tiles)
 void nf_launch_gemm_nt_masked(const void* x, long ldx, const void* W, long ldw, const void* bias,

@@ -216,6 +216,164 @@ __global__ void __launch_bounds__(256) planar_bwd_kernel(PlanarArgs a) {
   }
 }
 
+// ---- inverse (paper variant only: w.u_hat >= -1 makes every layer a bijection) ----
+//
+// Layers are undone from K-1 down to 0. For one layer, s = w.x is the unique root of
+//   g(s) = s + c tanh(s + b) - t,   c = w.u_hat,  t = w.y,   g' = psi = 1 + c (1 - tanh^2) >= 0,
+// and lies in [t - |c|, t + |c|]; then x = y - u_hat tanh(s + b) and the inverse log-det term
+// is -log(|psi| + eps), minus the forward's guarded term at the preimage.
+//
+// The solve has compile-time trip counts (no data-dependent exit): kInvBisect halvings take the
+// bracket 2|c| below one fp32 ulp of |c|, then kInvNewton Newton steps, each clamped to the
+// final bracket, polish the root where psi is not small. NaN inputs fall through the compares
+// and come out as NaN. In the wave-per-row mapping the reductions leave t, c and b identical in
+// all 64 lanes, so every lane solves the same scalar.
+constexpr int kInvBisect = 30;
+constexpr int kInvNewton = 2;
+
+__device__ __forceinline__ float planar_root(float t, float c, float b) {
+  float lo = t - fabsf(c), hi = t + fabsf(c);
+#pragma unroll 1
+  for (int it = 0; it < kInvBisect; ++it) {
+    const float mid = 0.5f * (lo + hi);
+    const float gm = mid + c * tanhf(mid + b) - t;
+    if (gm > 0.f) hi = mid; else lo = mid;
+  }
+  float s = 0.5f * (lo + hi);
+#pragma unroll
+  for (int it = 0; it < kInvNewton; ++it) {
+    const float h = tanhf(s + b);
+    const float psi = 1.f + c * (1.f - h * h);
+    const float sn = s - (s + c * h - t) / fmaxf(psi, 1e-30f);
+    s = fminf(fmaxf(sn, lo), hi);
+  }
+  return s;
+}
+
+// a.z = y, a.zK = x, a.saved[k] = the preimage under layer k (the image the forward kernel
+// saves as that layer's input), a.ldj = log|det dx/dy|
+template <bool WROW, int PER>
+__global__ void __launch_bounds__(256) planar_inv_kernel(PlanarArgs a) {
+  long row;
+  int lane;
+  if (!row_of<WROW, PER>(a, row, lane)) return;
+  const int D = a.D;
+  float z[PER];
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    const int j = elem<WROW, PER>(i, lane);
+    z[i] = j < D ? a.z[row * D + j] : 0.f;
+  }
+  float ldj = 0.f;
+  for (int k = a.K - 1; k >= 0; --k) {
+    const long pbase = a.per_sample ? ((long)k * a.N + row) * D : (long)k * D;
+    const float b = a.per_sample ? a.Bv[(long)k * a.N + row] : a.Bv[k];
+    float u[PER];
+    float t = 0.f, c = 0.f;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int j = elem<WROW, PER>(i, lane);
+      const float w = j < D ? a.W[pbase + j] : 0.f;
+      u[i] = j < D ? a.U[pbase + j] : 0.f;
+      t += z[i] * w;
+      c += w * u[i];
+    }
+    t = rsum<WROW>(t);
+    c = rsum<WROW>(c);
+    const float s = planar_root(t, c, b);
+    const float h = tanhf(s + b);
+    const float psi = 1.f + c * (1.f - h * h);
+    float* sv = a.saved + ((long)k * a.N + row) * D;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int j = elem<WROW, PER>(i, lane);
+      z[i] -= u[i] * h;
+      if (j < D) sv[j] = z[i];
+    }
+    ldj -= __logf(fabsf(psi) + kPsiEps);
+  }
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    const int j = elem<WROW, PER>(i, lane);
+    if (j < D) a.zK[row * D + j] = z[i];
+  }
+  if (!WROW || lane == 0) a.ldj[row] = ldj;
+}
+
+// Backward of the inverse. Upstream a.gz = dLoss/dx, a.gl = dLoss/dldj. Per layer (0 .. K-1, the
+// reverse of the order the inverse applied them), with x = saved[k], a = w.x + b, h = tanh(a):
+//   ip = sign(psi) / (|psi| + eps),  La = -ip h'' c,  Lc = -ip h'      (the layer's log-det term)
+//   gbar = gx + gL La w                                   (x also feeds the log-det through a)
+//   v = gbar - h' w (u_hat.gbar) ip                       ((I + h' u_hat w^T)^-T gbar, guarded)
+//   gy = v,  gu_hat = -h v + gL Lc w,  gw = -h' (u_hat.v) x + gL (La x + Lc u_hat),
+//   gb = -h' (u_hat.v) + gL La
+template <bool WROW, int PER>
+__global__ void __launch_bounds__(256) planar_inv_bwd_kernel(PlanarArgs a) {
+  long row;
+  int lane;
+  if (!row_of<WROW, PER>(a, row, lane)) return;
+  const int D = a.D;
+  float g[PER];
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    const int j = elem<WROW, PER>(i, lane);
+    g[i] = j < D ? a.gz[row * D + j] : 0.f;
+  }
+  const float gL = a.gl[row];
+  for (int k = 0; k < a.K; ++k) {
+    const long pbase = a.per_sample ? ((long)k * a.N + row) * D : (long)k * D;
+    const float b = a.per_sample ? a.Bv[(long)k * a.N + row] : a.Bv[k];
+    const float* sv = a.saved + ((long)k * a.N + row) * D;
+    float w[PER], u[PER], x[PER];
+    float dot = 0.f, eta = 0.f, gu = 0.f;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int j = elem<WROW, PER>(i, lane);
+      if (j < D) {
+        w[i] = a.W[pbase + j];
+        u[i] = a.U[pbase + j];
+        x[i] = sv[j];
+      } else {
+        w[i] = u[i] = x[i] = 0.f;
+      }
+      dot += x[i] * w[i];
+      eta += w[i] * u[i];
+      gu += g[i] * u[i];
+    }
+    dot = rsum<WROW>(dot);
+    eta = rsum<WROW>(eta);
+    gu = rsum<WROW>(gu);
+    const float h = tanhf(dot + b);
+    const float hp = 1.f - h * h;
+    const float hpp = -2.f * h * hp;
+    const float ip = dlog_guard(1.f + hp * eta);
+    const float la = -ip * hpp * eta * gL;   // gL dL/da
+    const float lc = -ip * hp * gL;          // gL dL/dc
+    // u_hat.gbar = u_hat.gx + la c;  v = gbar - kv w  ->  u_hat.v = u_hat.gbar - kv c
+    const float ugb = gu + la * eta;
+    const float kv = hp * ugb * ip;
+    const float uv = ugb - kv * eta;
+    const float db = -hp * uv + la;
+    float* dWr = a.dW + ((long)k * a.N + row) * D;
+    float* dUr = a.dU + ((long)k * a.N + row) * D;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int j = elem<WROW, PER>(i, lane);
+      g[i] += (la - kv) * w[i];
+      if (j < D) {
+        dUr[j] = -h * g[i] + lc * w[i];
+        dWr[j] = db * x[i] + lc * u[i];
+      }
+    }
+    if (!WROW || lane == 0) a.dB[(long)k * a.N + row] = db;
+  }
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    const int j = elem<WROW, PER>(i, lane);
+    if (j < D) a.dz[row * D + j] = g[i];
+  }
+}
+
 // Shared (non-amortized) parameters, D <= 16, K * PER <= 256: the backward recomputes every
 // layer's input from z0 into LDS (no [K][N][D] saved-state buffer in HBM) and reduces the
 // parameter gradients inside the kernel: one wave per block walks rows (grid-stride), each
@@ -355,18 +513,24 @@ static void launch_planar_shared(const PlanarArgs& a, float* part, int nblk, hip
   NF_HIP_CHECK(hipGetLastError());
 }
 
+enum PlanarKind { kPlanarFwd, kPlanarBwd, kPlanarInv, kPlanarInvBwd };
+
 template <bool WROW, int PER>
-static void launch_planar(const PlanarArgs& a, bool bwd, hipStream_t stream) {
+static void launch_planar(const PlanarArgs& a, PlanarKind kind, hipStream_t stream) {
   const long threads = WROW ? (long)a.N * 64 : (long)a.N;
   dim3 grid((unsigned)((threads + 255) / 256)), block(256);
-  if (bwd)
+  if (kind == kPlanarBwd)
     hipLaunchKernelGGL((planar_bwd_kernel<WROW, PER>), grid, block, 0, stream, a);
+  else if (kind == kPlanarInv)
+    hipLaunchKernelGGL((planar_inv_kernel<WROW, PER>), grid, block, 0, stream, a);
+  else if (kind == kPlanarInvBwd)
+    hipLaunchKernelGGL((planar_inv_bwd_kernel<WROW, PER>), grid, block, 0, stream, a);
   else
     hipLaunchKernelGGL((planar_fwd_kernel<WROW, PER>), grid, block, 0, stream, a);
   NF_HIP_CHECK(hipGetLastError());
 }
 
-static void dispatch_planar(const PlanarArgs& a, bool bwd, hipStream_t stream) {
+static void dispatch_planar(const PlanarArgs& a, PlanarKind bwd, hipStream_t stream) {
   const int D = a.D;
   if (D <= 2) return launch_planar<false, 2>(a, bwd, stream);
   if (D <= 4) return launch_planar<false, 4>(a, bwd, stream);
@@ -390,7 +554,7 @@ void nf_launch_planar_fwd(const float* z, const float* W, const float* U, const 
   PlanarArgs a{};
   a.z = z; a.W = W; a.U = U; a.Bv = B; a.zK = zK; a.ldj = ldj; a.saved = saved;
   a.N = N; a.D = D; a.K = K; a.per_sample = per_sample; a.broadcast = broadcast;
-  dispatch_planar(a, false, stream);
+  dispatch_planar(a, kPlanarFwd, stream);
 }
 
 void nf_launch_planar_bwd(const float* saved, const float* W, const float* U, const float* B,
@@ -402,7 +566,28 @@ void nf_launch_planar_bwd(const float* saved, const float* W, const float* U, co
   a.saved = (float*)saved; a.W = W; a.U = U; a.Bv = B; a.gz = gz; a.gl = gl; a.dz = dz;
   a.dW = dW; a.dU = dU; a.dB = dB;
   a.N = N; a.D = D; a.K = K; a.per_sample = per_sample; a.broadcast = broadcast;
-  dispatch_planar(a, true, stream);
+  dispatch_planar(a, kPlanarBwd, stream);
+}
+
+void nf_launch_planar_inv(const float* y, const float* W, const float* U, const float* B, float* x,
+                          float* ldj, float* saved, int N, int D, int K, int per_sample,
+                          hipStream_t stream) {
+  if (N <= 0) return;
+  PlanarArgs a{};
+  a.z = y; a.W = W; a.U = U; a.Bv = B; a.zK = x; a.ldj = ldj; a.saved = saved;
+  a.N = N; a.D = D; a.K = K; a.per_sample = per_sample;
+  dispatch_planar(a, kPlanarInv, stream);
+}
+
+void nf_launch_planar_inv_bwd(const float* saved, const float* W, const float* U, const float* B,
+                              const float* gx, const float* gl, float* dy, float* dW, float* dU,
+                              float* dB, int N, int D, int K, int per_sample, hipStream_t stream) {
+  if (N <= 0) return;
+  PlanarArgs a{};
+  a.saved = (float*)saved; a.W = W; a.U = U; a.Bv = B; a.gz = gx; a.gl = gl; a.dz = dy;
+  a.dW = dW; a.dU = dU; a.dB = dB;
+  a.N = N; a.D = D; a.K = K; a.per_sample = per_sample;
+  dispatch_planar(a, kPlanarInvBwd, stream);
 }
 
 int nf_planar_shared_per(int D) { return D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : 0; }

@@ -4,4 +4,5 @@ from vi_normflows_amd.flows import (IAF, MAF, MADE, AffineCoupling, DiagAffine, 
                                     FlowSequence, Planar, PlanarStack, Radial, RadialStack,
                                     RealNVP, RQSCoupling, NeuralSplineFlow,
                                     SylvesterStack, AmortizedSylvester, DSFCoupling,
-                                    DSFAutoregressive, NeuralAutoregressiveFlow)
+                                    DSFAutoregressive, NeuralAutoregressiveFlow,
+                                    planar_stack_inverse, radial_stack_inverse)

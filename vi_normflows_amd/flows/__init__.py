@@ -6,8 +6,10 @@ from .coupling import AffineCoupling, RealNVP, coupling_transform
 from .made import IAF, MADE, MAF, MaskedLinear, made_degrees, made_masks
 from .naf import DSFAutoregressive, DSFCoupling, NeuralAutoregressiveFlow
 from .planar import (AmortizedPlanar, Planar, PlanarStack, get_uhat, m, planar_flow,
-                     planar_stack, planar_stack_reference)
+                     planar_stack, planar_stack_inverse, planar_stack_inverse_reference,
+                     planar_stack_reference)
 from .radial import (AmortizedRadial, Radial, RadialStack, radial_params, radial_stack,
+                     radial_stack_inverse, radial_stack_inverse_reference,
                      radial_stack_reference)
 from .spline import NeuralSplineFlow, RQSCoupling
 from .sylvester import AmortizedSylvester, SylvesterStack
@@ -20,4 +22,6 @@ __all__ = [
     "AmortizedRadial", "radial_params", "radial_stack", "radial_stack_reference",
     "RQSCoupling", "NeuralSplineFlow", "SylvesterStack", "AmortizedSylvester",
     "DSFCoupling", "DSFAutoregressive", "NeuralAutoregressiveFlow",
+    "planar_stack_inverse", "planar_stack_inverse_reference", "radial_stack_inverse",
+    "radial_stack_inverse_reference",
 ]

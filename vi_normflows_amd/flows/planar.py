@@ -96,6 +96,117 @@ def planar_stack_reference(z, W, U, B, variant="paper", ldj="exact", uhat_norm="
     return z, ld
 
 
+INV_BISECTIONS = 60   # composite solve: bracket 2|c| halved to below fp64 resolution
+INV_NEWTON = 4
+
+
+def _planar_root(t, c, b):
+    """s with s + c tanh(s + b) = t (no autograd): bisection on [t - |c|, t + |c|], then Newton
+    steps clamped to the remaining bracket. c >= -1 makes the left side monotone."""
+    lo, hi = t - c.abs(), t + c.abs()
+    for _ in range(INV_BISECTIONS):
+        mid = 0.5 * (lo + hi)
+        up = mid + c * torch.tanh(mid + b) - t > 0
+        lo, hi = torch.where(up, lo, mid), torch.where(up, mid, hi)
+    s = 0.5 * (lo + hi)
+    for _ in range(INV_NEWTON):
+        h = torch.tanh(s + b)
+        psi = 1.0 + c * (1.0 - h * h)
+        step = (s + c * h - t) / psi.clamp_min(1e-30)
+        s = torch.minimum(torch.maximum(s - step, lo), hi)
+    return s
+
+
+def planar_stack_inverse_reference(y, W, U, B, uhat_norm="sq"):
+    """Composite inverse of the K-layer paper-variant stack: (x, log|det dx/dy|) with
+    ``planar_stack_reference(x, W, U, B) == (y, -ldj)``. Layers are undone from K-1 down to 0.
+
+    Per layer, s = w.x is the root of s + c tanh(s + b) = w.y (c = w.u_hat >= -1), found without
+    autograd; one differentiable Newton step around that constant carries the exact
+    implicit-function gradients in y, W, U and B. The log-det term is minus the forward's
+    guarded log(|psi| + 1e-7) at the preimage."""
+    ld = torch.zeros(y.shape[0], dtype=y.dtype, device=y.device)
+    for k in range(W.shape[0] - 1, -1, -1):
+        w, b = W[k], B[k]
+        uh = get_uhat(U[k], w, uhat_norm)
+        c = (w * uh).sum(-1)
+        t = (y * w).sum(-1)
+        with torch.no_grad():
+            s0 = _planar_root(t, c, b)
+        h0 = torch.tanh(s0 + b)
+        psi0 = 1.0 + c * (1.0 - h0 * h0)
+        # psi = 0 exactly (c = -1 at a = 0): a triple root, the step would divide by zero
+        s = s0 - (s0 + c * h0 - t) / torch.where(psi0.detach() > 0, psi0, torch.ones_like(psi0))
+        hv = torch.tanh(s + b)
+        y = y - uh * hv.unsqueeze(-1)
+        ld = ld - torch.log(EPS + torch.abs(1.0 + c * (1.0 - hv * hv)))
+    return y, ld
+
+
+class _PlanarStackInvFn(torch.autograd.Function):
+    """Fused HIP inverse of the paper-variant stack (``planar_inv_kernel`` /
+    ``planar_inv_bwd_kernel``). The kernel saves every layer's preimage [K, N, D]; the backward
+    recomputes a / h / psi from it and writes per-row parameter gradients, summed here over rows
+    for shared parameters."""
+
+    @staticmethod
+    def forward(ctx, y, W, Uh, B):
+        from ..ops._ext import native
+
+        K = W.shape[0]
+        N, D = y.shape
+        per_sample = W.dim() == 3
+        yc = y.contiguous().float()
+        Wc, Uc, Bc = W.contiguous().float(), Uh.contiguous().float(), B.contiguous().float()
+        x = torch.empty_like(yc)
+        ldj = torch.empty(N, device=y.device, dtype=torch.float32)
+        saved = torch.empty(K, N, D, device=y.device, dtype=torch.float32)
+        native().planar_stack_inv(yc, Wc, Uc, Bc, per_sample, False, x, ldj, saved)
+        ctx.save_for_backward(saved, Wc, Uc, Bc)
+        ctx.per_sample = per_sample
+        return x, ldj
+
+    @staticmethod
+    def backward(ctx, gx, gldj):
+        from ..ops._ext import native
+
+        saved, W, Uh, B = ctx.saved_tensors
+        K, N, D = saved.shape
+        gx = (gx if gx is not None else torch.zeros(N, D, device=W.device)).contiguous().float()
+        gl = (gldj if gldj is not None else torch.zeros(N, device=W.device)).contiguous().float()
+        dy = torch.empty(N, D, device=W.device, dtype=torch.float32)
+        dW = torch.empty(K, N, D, device=W.device, dtype=torch.float32)
+        dU = torch.empty(K, N, D, device=W.device, dtype=torch.float32)
+        dB = torch.empty(K, N, device=W.device, dtype=torch.float32)
+        native().planar_stack_inv_bwd(saved, W, Uh, B, ctx.per_sample, False, gx, gl, dy, dW, dU,
+                                      dB)
+        if not ctx.per_sample:
+            dW, dU, dB = dW.sum(1), dU.sum(1), dB.sum(1)
+        return dy, dW, dU, dB
+
+
+def planar_stack_inverse(y, W, U, B, uhat_norm="sq"):
+    """Inverse of K paper-variant planar layers, ``(x, log|det dx/dy|)``: fused HIP kernel on GPU
+    fp32, composite otherwise."""
+    if y.is_cuda and y.dtype == torch.float32:
+        return _PlanarStackInvFn.apply(y, W, get_uhat(U, W, uhat_norm), B)
+    return planar_stack_inverse_reference(y, W, U, B, uhat_norm)
+
+
+def _check_invertible(variant, ldj, uhat_norm):
+    """The inverse needs w.u_hat >= -1 (``uhat_norm="sq"``) for the paper transform and its
+    exact log-det; the compatibility options have no guaranteed inverse."""
+    if variant != "paper":
+        raise NotImplementedError(f'variant="{variant}" planar flows have no guaranteed inverse '
+                                  '(variant="paper" only)')
+    if uhat_norm != "sq":
+        raise NotImplementedError(f'uhat_norm="{uhat_norm}" does not keep w.u_hat >= -1: no '
+                                  'inverse (uhat_norm="sq" only)')
+    if ldj != "exact":
+        raise NotImplementedError(f'ldj="{ldj}" is not the log-det of the transform: no inverse '
+                                  'log-det (ldj="exact" only)')
+
+
 class _PlanarStackFn(torch.autograd.Function):
     """Fused HIP planar stack (paper/broadcast update, exact log-det with the reference's
     log(|psi| + 1e-7) guard).
@@ -186,8 +297,16 @@ class PlanarStack(Flow):
             B = torch.zeros(K)
         self.W, self.U, self.B = nn.Parameter(W), nn.Parameter(U), nn.Parameter(B)
 
+    @property
+    def invertible(self):  # type: ignore[override]
+        return (self.variant, self.uhat_norm, self.ldj_mode) == ("paper", "sq", "exact")
+
     def forward(self, z, context=None):
         return planar_stack(z, self.W, self.U, self.B, self.variant, self.ldj_mode, self.uhat_norm)
+
+    def inverse(self, y, context=None):
+        _check_invertible(self.variant, self.ldj_mode, self.uhat_norm)
+        return planar_stack_inverse(y, self.W, self.U, self.B, self.uhat_norm)
 
     def uhat(self):
         return get_uhat(self.U, self.W, self.uhat_norm)
@@ -221,6 +340,15 @@ class AmortizedPlanar(Flow):
         W, U, B = context
         return planar_stack(z, W, U, B, self.variant, self.ldj_mode, self.uhat_norm)
 
+    @property
+    def invertible(self):  # type: ignore[override]
+        return (self.variant, self.uhat_norm, self.ldj_mode) == ("paper", "sq", "exact")
+
+    def inverse(self, y, context=None):
+        _check_invertible(self.variant, self.ldj_mode, self.uhat_norm)
+        W, U, B = context
+        return planar_stack_inverse(y, W, U, B, self.uhat_norm)
+
 
 def planar_log_det_check(z, w, u, b, variant="paper"):
     """Exact log|det J| via autograd Jacobian (testing helper)."""
@@ -235,4 +363,5 @@ def planar_log_det_check(z, w, u, b, variant="paper"):
 
 
 __all__ = ["m", "get_uhat", "planar_flow", "planar_stack", "planar_stack_reference",
+           "planar_stack_inverse", "planar_stack_inverse_reference",
            "PlanarStack", "Planar", "AmortizedPlanar", "EPS", "math"]

@@ -121,6 +121,30 @@ def fit_flow_vi(target="U1", flow="planar", K: int = 8, iters: int = 10000, lr: 
     return FlowVIResult(fl, model.base, tgt, hist, model.metrics(max(1000, n_samples), g))
 
 
+def fit_density(flow, data, base=None, iters: int = 1000, lr: float = 1e-2, batch=None,
+                generator=None):
+    """Maximum-likelihood (forward-KL) fit of an invertible flow to samples: Adam on the mean
+    negative ``log_prob`` of ``data`` under ``FlowDistribution(base, flow)`` (``base`` defaults to
+    a standard normal of the data's dimension). ``batch`` draws that many rows per step instead
+    of using all of them. Returns the loss trace (one float per step)."""
+    from ..flows.base import FlowDistribution
+
+    dist = FlowDistribution(base if base is not None else StdNormal(data.shape[1]), flow)
+    opt = torch.optim.Adam([p for p in dist.parameters() if p.requires_grad], lr=lr)
+    trace = []
+    for _ in range(iters):
+        x = data
+        if batch is not None and batch < data.shape[0]:
+            idx = torch.randint(data.shape[0], (batch,), generator=generator)
+            x = data[idx.to(data.device)]
+        loss = -dist.log_prob(x).mean()
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+        trace.append(float(loss.detach()))
+    return trace
+
+
 def optimise(func, num_samples: int, num_iter: int, lr: float, K: int, dim_z: int = 2,
              optimizer: str = "rmsprop", verbose: bool = True, device="cpu", seed: int = 0):
     """``get_data.optimise`` signature: planar VI with W=U=b=0.1 init, RMSProp (get_data.py:119-142).

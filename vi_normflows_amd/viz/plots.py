@@ -123,6 +123,26 @@ def plot_density_and_samples(target, samples, lims=(-4, 4), n=200, path=None, ti
     return fig
 
 
+def plot_flow_density(flow_dist, lims=(-4, 4), n=200, path=None, title=None):
+    """Exact density exp(log_prob) of an invertible 2-D ``FlowDistribution`` on an n x n grid
+    (no KDE of samples)."""
+    plt = _plt()
+    fig, ax = plt.subplots(1, 1, figsize=(6, 6))
+    g1, g2, z = _grid(lims[0], lims[1], n)
+    p = next(iter(flow_dist.parameters()), None)
+    if p is not None:
+        z = z.to(device=p.device, dtype=p.dtype)
+    with torch.no_grad():
+        d = _np(torch.exp(flow_dist.log_prob(z))).reshape(n, n)
+    ax.pcolormesh(g1, g2, d, cmap=plt.cm.Reds, shading="auto")
+    ax.set_xlim(lims)
+    ax.set_ylim(lims)
+    if title:
+        ax.set_title(title)
+    _save(fig, path)
+    return fig
+
+
 def plot_loss(values, path=None, ylabel="free energy", floor=None):
     plt = _plt()
     fig, ax = plt.subplots(1, 1, figsize=(8, 4))
