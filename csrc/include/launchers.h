@@ -63,6 +63,19 @@ void nf_launch_sylvester_bwd(const float* saved, const NfSylParams& p, const uns
                              const float* gz, const float* gl, float* dz, const NfSylGrads& g,
                              int N, int D, int K, int H, hipStream_t stream);
 
+// stein.hip: all-pairs SVGD direction and Stein-kernel row sums (KSD), fp32, 1 <= D <= 64.
+// x / score [N, D] with row strides ldx / lds in elements and unit inner stride; the bandwidth is
+// *h_dev when h_dev is not null, else h_host; kind 0 = rbf, 1 = imq. S = nf_stein_splits(N, D,
+// j_splits) partial sums per output element go through work ([S, N, D] floats for svgd, [S, N]
+// for ksd) and are added in fixed order; phi [N, D], rows / diag [N] dense, every entry written.
+int nf_stein_splits(int N, int D, int j_splits);   // j_splits = 0: chosen from (N, D) alone
+void nf_launch_stein_svgd(const float* x, long ldx, const float* score, long lds,
+                          const float* h_dev, float h_host, int kind, int S, float* phi,
+                          float* work, int N, int D, hipStream_t stream);
+void nf_launch_stein_ksd(const float* x, long ldx, const float* score, long lds,
+                         const float* h_dev, float h_host, int kind, int S, float* rows,
+                         float* diag, float* work, int N, int D, hipStream_t stream);
+
 // elbo.hip
 void nf_launch_target_logp_grad(int kind, const float* A, long lda, const float* Bh, long ldb,
                                 float* gA, long ldga, float* gB, long ldgb, int grad_accumulate,

@@ -433,3 +433,76 @@ def sylvester_stack_reference(z, R1, R2, d1, d2, b, V, flips):
         z = z + sylvester_basis_apply(y, Vk, flip, transpose=False)
         ld = ld + torch.log(torch.abs(1.0 + (1.0 - h * h) * e1 * e2) + SYL_EPS).sum(-1)
     return z, ld
+
+
+# -------------------------------------------------------------------- stein
+STEIN_KINDS = {"rbf": 0, "imq": 1}
+
+
+def _stein_h(h, x):
+    if isinstance(h, torch.Tensor):
+        return h.detach().reshape(()).to(device=x.device, dtype=x.dtype)
+    return torch.tensor(float(h), device=x.device, dtype=x.dtype)
+
+
+def stein_kernel_terms_reference(r2, h, kernel: str = "rbf"):
+    """``(f, f', f'')`` of ``r2 = |x_i - x_j|^2`` for the two Stein kernel functions:
+    ``"rbf"`` f = exp(-r2 / h), ``"imq"`` f = (h + r2)^(-1/2)."""
+    if kernel == "rbf":
+        f = torch.exp(-r2 / h)
+        return f, -f / h, f / (h * h)
+    if kernel == "imq":
+        t = h + r2
+        return t ** -0.5, -0.5 * t ** -1.5, 0.75 * t ** -2.5
+    raise ValueError(f"stein: kernel must be rbf or imq, got {kernel!r}")
+
+
+def svgd_direction_reference(x, score, h, kernel: str = "rbf", chunk: int = 1024,
+                             return_abs: bool = False):
+    """SVGD direction ``phi_i = (1/N) sum_j [f_ij s_j - 2 f'_ij (x_i - x_j)]`` in the dtype of
+    ``x``, ``chunk`` rows i at a time (memory O(chunk N D)). ``return_abs=True`` also returns
+    ``A_i = (1/N) sum_j (|f_ij s_j| + |2 f'_ij (x_i - x_j)|)``, elementwise: the scale an
+    implementation's rounding error is measured against."""
+    N, D = x.shape
+    x, score = x.detach(), score.detach().to(x.dtype)
+    hh = _stein_h(h, x)
+    phi = torch.empty_like(x)
+    A = torch.empty_like(x) if return_abs else None
+    for i0 in range(0, N, chunk):
+        i1 = min(i0 + chunk, N)
+        d = x[i0:i1, None, :] - x[None, :, :]
+        f, fp, _ = stein_kernel_terms_reference((d * d).sum(-1), hh, kernel)
+        phi[i0:i1] = (f @ score - 2.0 * (fp[..., None] * d).sum(1)) / N
+        if return_abs:
+            A[i0:i1] = (f.abs() @ score.abs() + 2.0 * (fp.abs()[..., None] * d.abs()).sum(1)) / N
+    return (phi, A) if return_abs else phi
+
+
+def ksd_rows_reference(x, score, h, kernel: str = "imq", chunk: int = 1024,
+                       return_abs: bool = False):
+    """Row sums and diagonal of the Stein kernel matrix ``u_ij = f s_i.s_j + 2 f' (s_j - s_i).
+    (x_i - x_j) - 2 D f' - 4 f'' r2``: ``(rows, diag)`` with ``rows[i] = sum_j u_ij`` and
+    ``diag[i] = u_ii``, ``chunk`` rows at a time. ``return_abs=True`` appends ``B_i = sum_j (|f
+    s_i.s_j| + |2 f' (s_j - s_i).(x_i - x_j)| + |2 D f'| + |4 f'' r2|)``."""
+    N, D = x.shape
+    x, score = x.detach(), score.detach().to(x.dtype)
+    hh = _stein_h(h, x)
+    rows = torch.empty(N, dtype=x.dtype, device=x.device)
+    diag = torch.empty_like(rows)
+    B = torch.empty_like(rows) if return_abs else None
+    for i0 in range(0, N, chunk):
+        i1 = min(i0 + chunk, N)
+        d = x[i0:i1, None, :] - x[None, :, :]
+        r2 = (d * d).sum(-1)
+        f, fp, fpp = stein_kernel_terms_reference(r2, hh, kernel)
+        t1 = f * (score[i0:i1] @ score.T)
+        t2 = 2.0 * fp * ((score[None, :, :] - score[i0:i1, None, :]) * d).sum(-1)
+        t3 = 2.0 * D * fp
+        t4 = 4.0 * fpp * r2
+        u = t1 + t2 - t3 - t4
+        rows[i0:i1] = u.sum(1)
+        diag[i0:i1] = u[torch.arange(i1 - i0, device=x.device),
+                        torch.arange(i0, i1, device=x.device)]
+        if return_abs:
+            B[i0:i1] = (t1.abs() + t2.abs() + t3.abs() + t4.abs()).sum(1)
+    return (rows, diag, B) if return_abs else (rows, diag)
