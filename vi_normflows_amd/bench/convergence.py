@@ -37,8 +37,7 @@ def run(batch: int, steps: int, every: int = 10, layers: int = 32, dim: int = 78
         rec = dict(step=int(eng.step_t.item()), F=float(eng.loss.item()),
                    logq0=float(eng.logq0.mean().item()), ldj=float(eng.ldj.mean().item()),
                    logp=float(eng.logp.mean().item()), beta=float(eng.beta.item()),
-                   grad_norm=float(eng.gnorm2.item()) ** 0.5, skipped=float(eng.n_skipped.item()),
-                   batch=batch, wall_s=round(time.perf_counter() - t0, 3), lr=lr,
+                   **eng.log_record(), batch=batch, wall_s=round(time.perf_counter() - t0, 3), lr=lr,
                    pairing=pairing, target=target)
         recs.append(rec)
         if out is not None:

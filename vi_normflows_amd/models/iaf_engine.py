@@ -31,13 +31,13 @@ import torch
 
 from ..ops import fused, gemm
 from ..utils.flat import FlatLayout, FlatParams
-from ..utils.profiling import trace_range
+from .engine_core import FlatEngine, anneal_beta
 from .iaf_vae import IAFVAE, IAFVAEConfig
 
 LOG2PI = math.log(2 * math.pi)
 
 
-class IAFEngine:
+class IAFEngine(FlatEngine):
     """Explicit-backward IAF VAE step on flat buffers. ``data``: fp32 [n_batches * B, dim_x]
     binary images held on the device; step t trains on batch t mod n_batches.
 
@@ -46,6 +46,9 @@ class IAFEngine:
     ``"theano"`` (beta_t = min(1, 0.01 + t / 1e4), theano_implement.py:169-175). beta_t and the
     two coefficients it scales (likelihood-logit gradient, prior gradient) are device scalars
     updated inside the captured step, so an annealed run replays one hipGraph."""
+
+    supports_forward_persist = True
+    trace_forward, trace_backward = "iaf_forward", "iaf_backward"
 
     def __init__(self, cfg: IAFVAEConfig, batch: int, data: torch.Tensor, device="cuda",
                  seed: int = 0, rank: int = 0, lr: float = 3e-4, betas=(0.9, 0.999),
@@ -56,18 +59,12 @@ class IAFEngine:
         self.device = torch.device(device)
         self.cdt = torch.bfloat16 if self.device.type == "cuda" else torch.float32
         self.seed, self.rank = int(seed), int(rank)
-        # update rule: adam | rmsprop | sgd | rmsprop_momentum (fused flat kernel, optim.hip)
-        self.opt = fused.resolve_optimizer(optimizer, betas, eps)
-        self.lr, self.beta = lr, float(beta)
-        self.betas, self.eps = (self.opt.b1, self.opt.b2), self.opt.eps
+        self._init_core(optimizer, betas, eps, lr, max_grad_norm=max_grad_norm)
+        self.beta = float(beta)
         if anneal not in ("none", "reference", "theano"):
             raise ValueError(f"IAFEngine anneal must be none | reference | theano, got {anneal!r}")
         self.anneal, self.anneal_iters = anneal, int(anneal_iters)
-        self.max_grad_norm = float(max_grad_norm)
-        self.grad_scale_host = 1.0
-        self.unit_ready_hook = None
         self.eps_override = None
-        self.persist_forward_only = False
         assert data.shape[0] % self.B == 0 and data.shape[1] == cfg.dim_x
         self.data = data.to(self.device, torch.float32).contiguous()
         self.n_batches = data.shape[0] // self.B
@@ -99,26 +96,18 @@ class IAFEngine:
                     for n, s in ((f"dec.W{i}", (o, k)), (f"dec.b{i}", (o,)))])
         self.layout = L
         self.params = FlatParams(L, self.device, self.cdt)
-        self.params.v_init = self.opt.v_init
+        self._alloc_state()
 
     def _alloc(self):
         cfg, B, dev, cdt = self.cfg, self.B, self.device, self.cdt
         H, dz, C, Hm, X, K = cfg.hidden, cfg.dim_z, cfg.context, cfg.made_hidden, cfg.dim_x, cfg.n_flows
         f32 = torch.float32
         e = lambda *s, dt=cdt: torch.empty(*s, dtype=dt, device=dev)  # noqa: E731
-        self.step_t = torch.zeros((), dtype=f32, device=dev)
-        self.rng_offset = torch.zeros((), dtype=torch.int64, device=dev)
         # beta_t and the coefficients it scales: dF/dlogits = lik_coef (x - sigmoid) with
         # lik_coef = -beta_t / B, the prior term's dF/dz_K = prior_coef z_K with beta_t / B
         self.beta_t = torch.full((), self.beta, dtype=f32, device=dev)
         self._lik_coef = torch.full((), -self.beta / self.B, dtype=f32, device=dev)
         self._prior_coef = torch.full((), self.beta / self.B, dtype=f32, device=dev)
-        self.loss = torch.zeros((), dtype=f32, device=dev)
-        self.gnorm2 = torch.zeros((), dtype=f32, device=dev)
-        self.skip = torch.zeros((), dtype=f32, device=dev)
-        self.gscale = torch.ones((), dtype=f32, device=dev)
-        self.n_skipped = torch.zeros((), dtype=f32, device=dev)
-        self._partials = torch.zeros(512, dtype=f32, device=dev)
         self._rows = torch.arange(B, device=dev)
         self.xf = e(B, X, dt=f32)                 # the step's batch (fp32: likelihood operand)
         self.xb = e(B, X)                         # its bf16 copy (encoder GEMM operand)
@@ -308,10 +297,6 @@ class IAFEngine:
         F = self.lq - self.ldjk.sum(0) - self.beta_t * lp
         torch.mean(F, 0, out=self.loss)
 
-    def _hook(self, unit):
-        if self.unit_ready_hook is not None:
-            self.unit_ready_hook(unit)
-
     def backward(self):
         cfg, P, B = self.cfg, self.params, self.B
         dz, K = cfg.dim_z, cfg.n_flows
@@ -328,7 +313,7 @@ class IAFEngine:
         torch.mul(self.Z[K], self._prior_coef, out=cur[:, :dz])
         cur[:, dz:].zero_()
         gemm.linear_dgrad(self.dD[0], P.c("dec.W0"), cur[:, :dz], accumulate=True)
-        self._hook(K + 1)
+        self._mark_ready(K + 1)
         # IAF layers, top down: DX holds [dz_k | sum of the context gradients so far]; the gate
         # backward turns dz_{k+1} into its direct-path dz_k in place (each element is read
         # before it is written, by the same lane) and the MADE input gradient accumulates onto
@@ -343,7 +328,7 @@ class IAFEngine:
             # masked weight entries get a zero gradient (keeps them at zero under Adam)
             a, b = self.layout.unit_ranges[k + 1]
             P.grad[a:b].mul_(self.flow_mask[a - self._flow_lo:b - self._flow_lo])
-            self._hook(k + 1)
+            self._mark_ready(k + 1)
         # encoder output gradient [dmu | dlogvar | dh]
         dz0 = cur[:, :dz]
         self.dOenc[:, :dz].copy_(dz0)
@@ -355,64 +340,16 @@ class IAFEngine:
             (self.dOenc, self.A[1], P.g("enc.W2"), P.g("enc.b2")),
             (self.dA[1], self.A[0], P.g("enc.W1"), P.g("enc.b1")),
             (self.dA[0], self.xb, P.g("enc.W0"), P.g("enc.b0"))])
-        self._hook(0)
-
-    def optimizer_step(self):
-        P = self.params
-        fused.sumsq_guard(P.grad, self._partials, out_sumsq=self.gnorm2, skip=self.skip,
-                          scale=self.gscale, max_norm=self.max_grad_norm,
-                          base_scale=self.grad_scale_host)
-        b1, b2 = self.betas
-        fused.flat_optimizer(self.opt.kind, P.master, P.grad, P.m, P.v,
-                             pbf=None if P.compute is P.master else P.compute, lr=self.lr,
-                             b1=b1, b2=b2, eps=self.eps, wd=0.0, step=self.step_t,
-                             gscale=self.gscale, skip=self.skip)
-        self.n_skipped.add_(self.skip)
+        self._mark_ready(0)
 
     def _update_schedule(self):
         """Device-side step / beta_t update (captured into the step graph)."""
-        self.step_t.add_(1.0)      # Adam's bias correction reads the 1-based step
-        self.rng_offset.add_(1)
+        self._advance()
         if self.anneal == "none":
             return
-        if self.anneal == "reference":   # optimization.py:71-72, t = step - 1
-            cool, start = min(self.anneal_iters / 4.0, 1e4), 0.001
-        else:                            # theano_implement.py:169-175
-            cool, start = 1e4, 0.01
-        torch.clamp((self.step_t - 1.0) * (1.0 / cool) + start, max=1.0, out=self.beta_t)
+        anneal_beta(self.anneal, self.step_t, self.anneal_iters, self.beta_t)
         torch.mul(self.beta_t, -1.0 / self.B, out=self._lik_coef)
         torch.mul(self.beta_t, 1.0 / self.B, out=self._prior_coef)
-
-    def train_step(self, reduce_fn=None):
-        self._update_schedule()
-        fwd_persist = self.persist_forward_only and self.device.type == "cuda"
-        if fwd_persist:
-            # DP runner policy (parallel/runner.py): the persistent GEMM grid in the forward
-            # only - no collective is in flight there; the previous setting is restored
-            from ..ops._ext import native
-
-            prev = native().gemm_persist(1)
-            prev_r = native().gemm_grid_reserve(0)
-        with trace_range("iaf_forward"):
-            self.forward()
-        if fwd_persist:
-            native().gemm_persist(prev)
-            native().gemm_grid_reserve(prev_r)
-        with trace_range("iaf_backward"):
-            self.backward()
-        if reduce_fn is not None:
-            reduce_fn()
-        with trace_range("optimizer"):
-            self.optimizer_step()
-
-    def state_dict(self) -> dict:
-        return {"params": self.params.state_dict(), "step": self.step_t.detach().cpu(),
-                "rng_offset": self.rng_offset.detach().cpu(), "cfg": dict(self.cfg.__dict__)}
-
-    def load_state_dict(self, sd: dict) -> None:
-        self.params.load_state_dict(sd["params"])
-        self.step_t.copy_(sd["step"])
-        self.rng_offset.copy_(sd["rng_offset"])
 
     def flops_per_sample(self) -> float:
         """Dense-equivalent GEMM FLOPs per sample (forward + backward)."""

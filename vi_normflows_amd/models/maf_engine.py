@@ -38,7 +38,7 @@ from ..ops import fused
 from ..ops import gemm
 from ..utils.config import KernelPaths
 from ..utils.flat import FlatLayout, FlatParams
-from ..utils.profiling import trace_range
+from .engine_core import FlatEngine
 
 LOG2PI = math.log(2 * math.pi)
 
@@ -74,7 +74,10 @@ class MAFEngineConfig:
                                   math.log(self.banana_sigma2))
 
 
-class MAFEngine:
+class MAFEngine(FlatEngine):
+    # (no forward-only persistent grid: under DP the forward runs the runner's grid policy)
+    trace_forward, trace_backward = "maf_forward", "maf_backward"
+
     def __init__(self, cfg: MAFEngineConfig, batch: int, device="cuda", seed: int = 0,
                  rank: int = 0, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, max_grad_norm: float = 0.0, lr_warmup: float = 0.0,
@@ -86,13 +89,7 @@ class MAFEngine:
         self.cdt = torch.bfloat16 if gpu else torch.float32
         self.fp8 = gpu and cfg.precision == "fp8"
         self.seed, self.rank = int(seed), int(rank)
-        self.opt = fused.resolve_optimizer(optimizer, betas, eps)
-        self.lr, self.wd = lr, weight_decay
-        self.opt_kind, self.betas, self.eps = self.opt.kind, (self.opt.b1, self.opt.b2), self.opt.eps
-        self.max_grad_norm = float(max_grad_norm)
-        self.lr_warmup = float(lr_warmup)
-        self.grad_scale_host = 1.0
-        self.unit_ready_hook = None
+        self._init_core(optimizer, betas, eps, lr, weight_decay, max_grad_norm, lr_warmup)
         self.wgrad_fence_hook = None  # callable() before each weight-gradient launch (DP runner)
         self.data_override = None      # fixed data [B, D] (tests)
         D, H, L = cfg.dim, cfg.hidden, cfg.n_layers
@@ -104,7 +101,7 @@ class MAFEngine:
                              (f"l{l}.W2", (2 * D, H)), (f"l{l}.b2", (2 * D,))])
         self.layout = layout
         self.params = FlatParams(layout, self.device, self.cdt)
-        self.params.v_init = self.opt.v_init
+        self._alloc_state()
         s0, s1 = layout.slots["l0.W1"], layout.slots["l1.W1"] if L > 1 else None
         self.layer_stride = (s1.offset - s0.offset) if s1 is not None else layout.total
         self._build_masks()
@@ -143,14 +140,6 @@ class MAFEngine:
         cfg, B, dev = self.cfg, self.B, self.device
         D, H, L = cfg.dim, cfg.hidden, cfg.n_layers
         f32 = torch.float32
-        self.step_t = torch.zeros((), dtype=f32, device=dev)
-        self.rng_offset = torch.zeros((), dtype=torch.int64, device=dev)
-        self.loss = torch.zeros((), dtype=f32, device=dev)
-        self.gnorm2 = torch.zeros((), dtype=f32, device=dev)
-        self.skip = torch.zeros((), dtype=f32, device=dev)
-        self.gscale = torch.ones((), dtype=f32, device=dev)
-        self.n_skipped = torch.zeros((), dtype=f32, device=dev)
-        self._partials = torch.zeros(512, dtype=f32, device=dev)
         self.X = torch.empty(L + 1, B, D, dtype=f32, device=dev)          # x_0 .. u_L
         self.Xbf = torch.empty(L + 1, B, D, dtype=self.cdt, device=dev)
         self.Hbf = torch.empty(L, B, H, dtype=self.cdt, device=dev)        # relu(h) per layer
@@ -687,49 +676,15 @@ class MAFEngine:
                 P.g(f"l{l}.W2").mul_(mk["M2"])
                 P.g(f"l{l}.W1").mul_(mk["M1"])
             gu, gx = gx, gu
-            if self.unit_ready_hook is not None:
-                self.unit_ready_hook(l)
+            self._mark_ready(l)
 
-    # ------------------------------------------------------------------ optimizer / step
+    # ------------------------------------------------------------------ optimizer / checkpoint
     def optimizer_step(self):
-        P = self.params
-        fused.sumsq_guard(P.grad, self._partials, out_sumsq=self.gnorm2, skip=self.skip,
-                          scale=self.gscale, max_norm=self.max_grad_norm,
-                          base_scale=self.grad_scale_host)
-        b1, b2 = self.betas
-        fused.flat_optimizer(self.opt_kind, P.master, P.grad, P.m, P.v,
-                             pbf=None if P.compute is P.master else P.compute, lr=self.lr,
-                             b1=b1, b2=b2, eps=self.eps, wd=self.wd, step=self.step_t,
-                             gscale=self.gscale, skip=self.skip, warmup=self.lr_warmup)
-        self.n_skipped.add_(self.skip)
+        super().optimizer_step()
         if self.fp8:
             self.quantize_weights()
 
-    def _update_schedule(self):
-        self.step_t.add_(1.0)
-        self.rng_offset.add_(1)
-
-    def train_step(self, reduce_fn=None):
-        self._update_schedule()
-        with trace_range("maf_forward"):
-            self.forward()
-        with trace_range("maf_backward"):
-            self.backward()
-        if reduce_fn is not None:
-            with trace_range("grad_allreduce_wait"):
-                reduce_fn()
-        with trace_range("optimizer"):
-            self.optimizer_step()
-
-    # ------------------------------------------------------------------ utils
-    def state_dict(self) -> dict:
-        return {"params": self.params.state_dict(), "step": self.step_t.detach().cpu(),
-                "rng_offset": self.rng_offset.detach().cpu(), "cfg": self.cfg.__dict__}
-
-    def load_state_dict(self, sd: dict) -> None:
-        self.params.load_state_dict(sd["params"])
-        self.step_t.copy_(sd["step"])
-        self.rng_offset.copy_(sd["rng_offset"])
+    def _post_load(self):
         if self.fp8:
             self._wq_fresh = False
 

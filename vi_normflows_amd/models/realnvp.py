@@ -38,13 +38,7 @@ from ..ops import fused
 from ..ops import gemm
 from ..utils.config import KernelPaths
 from ..utils.flat import FlatLayout, FlatParams
-from ..utils.profiling import trace_range
-
-
-def _ext_native():
-    from ..ops._ext import native
-
-    return native()
+from .engine_core import FlatEngine, anneal_beta
 
 
 @dataclass
@@ -107,8 +101,11 @@ def _layer_shapes(cfg: RealNVPConfig):
     return [(dims[i + 1], dims[i]) for i in range(len(dims) - 1)]
 
 
-class RealNVPVI:
+class RealNVPVI(FlatEngine):
     """Explicit-backward RealNVP VI engine over flat parameter buffers."""
+
+    supports_forward_persist = True
+    trace_forward, trace_backward = "flow_forward+elbo", "flow_backward"
 
     def __init__(self, cfg: RealNVPConfig, batch: int, device="cuda",
                  compute_dtype: torch.dtype | None = None, seed: int = 0, rank: int = 0,
@@ -123,18 +120,9 @@ class RealNVPVI:
         self.cdt = compute_dtype
         self.seed = int(seed)
         self.rank = int(rank)
-        # update rule: adam | rmsprop | sgd | rmsprop_momentum (or an OPT_* kind), fused flat kernel
-        self.opt = fused.resolve_optimizer(optimizer, betas, eps)
-        self.lr, self.wd = lr, weight_decay
-        self.opt_kind, self.betas, self.eps = self.opt.kind, (self.opt.b1, self.opt.b2), self.opt.eps
-        self.max_grad_norm = float(max_grad_norm)
-        self.lr_warmup = float(lr_warmup)   # linear lr ramp over the first steps (device step)
-        self.grad_scale_host = 1.0
-        self.unit_ready_hook = None   # callable(unit_idx) after a unit's grads are final
+        self._init_core(optimizer, betas, eps, lr, weight_decay, max_grad_norm, lr_warmup)
         self.wgrad_fence_hook = None  # callable() before each weight-gradient launch (DP runner)
         self.eps_override = None      # fixed base noise [B, D] (tests); None -> Philox sampler
-        # DP runner: persistent GEMM grid in the forward only (parallel/runner.py)
-        self.persist_forward_only = False
 
         L = cfg.n_layers
         layout = FlatLayout()
@@ -147,24 +135,12 @@ class RealNVPVI:
             layout.add_unit(ts)
         self.layout = layout
         self.params = FlatParams(layout, self.device, self.cdt)
-        self.params.v_init = self.opt.v_init
         self._alloc_state()
+        self.beta = torch.ones((), dtype=torch.float32, device=self.device)
         self._alloc_workspace()
         self.init_params(seed)
 
     # ------------------------------------------------------------------ setup
-    def _alloc_state(self):
-        dev = self.device
-        self.step_t = torch.zeros((), dtype=torch.float32, device=dev)
-        self.rng_offset = torch.zeros((), dtype=torch.int64, device=dev)
-        self.beta = torch.ones((), dtype=torch.float32, device=dev)
-        self.loss = torch.zeros((), dtype=torch.float32, device=dev)
-        self.gnorm2 = torch.zeros((), dtype=torch.float32, device=dev)
-        self.skip = torch.zeros((), dtype=torch.float32, device=dev)
-        self.gscale = torch.ones((), dtype=torch.float32, device=dev)
-        self.n_skipped = torch.zeros((), dtype=torch.float32, device=dev)
-        self._partials = torch.zeros(512, dtype=torch.float32, device=dev)
-
     def _alloc_workspace(self):
         cfg, B, dev = self.cfg, self.B, self.device
         L, Dh, H, D = cfg.n_layers, cfg.half, cfg.hidden, cfg.dim
@@ -321,12 +297,9 @@ class RealNVPVI:
     # ------------------------------------------------------------------ schedule
     def _update_schedule(self):
         """Device-side step/beta update (captured into the graph)."""
-        self.step_t.add_(1.0)
-        self.rng_offset.add_(1)
+        self._advance()
         if self.cfg.anneal == "reference":
-            # beta_t = min(1, 0.001 + t / min(max_iter/4, 1e4))   (optimization.py:71-72)
-            cool = min(self.cfg.anneal_iters / 4.0, 1e4)
-            torch.clamp((self.step_t - 1.0) * (1.0 / cool) + 0.001, max=1.0, out=self.beta)
+            anneal_beta("reference", self.step_t, self.cfg.anneal_iters, self.beta)
         else:
             self.beta.fill_(1.0)
 
@@ -494,8 +467,7 @@ class RealNVPVI:
                     gemm.linear_dgrad(d, P.c(f"l{l}.W0"), self._G[l + 1], accumulate=True)
             wgrad_ready(l)
         self._base_backward()
-        if self.unit_ready_hook is not None:
-            self.unit_ready_hook(0)
+        self._mark_ready(0)
 
     def backward(self):
         if (self.wgrad_defer and self.wgrad_stream is None and gemm.backend() == "mfma"
@@ -533,21 +505,18 @@ class RealNVPVI:
                 side.wait_event(ready)
                 with torch.cuda.stream(side):
                     gemm.linear_wgrad_group(wg)
-                    if self.unit_ready_hook is not None:
-                        self.unit_ready_hook(l + 1)
+                    self._mark_ready(l + 1)
                     ev = torch.cuda.Event()
                     ev.record(side)
                 done[par] = ev
             else:
                 gemm.linear_wgrad_group(wg)
-                if self.unit_ready_hook is not None:
-                    self.unit_ready_hook(l + 1)
+                self._mark_ready(l + 1)
         for ev in done:
             if ev is not None:
                 main.wait_event(ev)
         self._base_backward()
-        if self.unit_ready_hook is not None:
-            self.unit_ready_hook(0)
+        self._mark_ready(0)
 
     def _base_backward(self):
         cfg, P = self.cfg, self.params
@@ -567,45 +536,6 @@ class RealNVPVI:
         sig = torch.exp(0.5 * P.p("base.logvar"))
         torch.sum(g0 * self.eps0, 0, out=glv)
         glv.mul_(0.5 * sig).sub_(0.5)
-
-    # ------------------------------------------------------------------ optimizer
-    def optimizer_step(self):
-        P = self.params
-        # non-finite guard (+ optional clipping); folds 1/world averaging into gscale
-        fused.sumsq_guard(P.grad, self._partials, out_sumsq=self.gnorm2, skip=self.skip,
-                          scale=self.gscale, max_norm=self.max_grad_norm,
-                          base_scale=self.grad_scale_host)
-        b1, b2 = self.betas
-        fused.flat_optimizer(self.opt_kind, P.master, P.grad, P.m, P.v,
-                             pbf=None if P.compute is P.master else P.compute, lr=self.lr,
-                             b1=b1, b2=b2, eps=self.eps, wd=self.wd, step=self.step_t,
-                             gscale=self.gscale, skip=self.skip, warmup=self.lr_warmup)
-        self.n_skipped.add_(self.skip)
-
-    # ------------------------------------------------------------------ step
-    def train_step(self, reduce_fn=None):
-        """One full ELBO step: sample, flow fwd, target, bwd, [grad all-reduce], optimizer."""
-        self._update_schedule()
-        fwd_persist = self.persist_forward_only and self.device.type == "cuda"
-        if fwd_persist:
-            # DP: no collective is in flight during the forward (the optimizer waited for every
-            # bucket), so the full one-block-per-CU persistent grid is safe there; the backward,
-            # where RCCL all-reduces hold CUs beside the GEMMs, runs the runner's policy (one
-            # block per tile, or a persistent grid with CUs reserved)
-            prev = _ext_native().gemm_persist(1)
-            prev_r = _ext_native().gemm_grid_reserve(0)
-        with trace_range("flow_forward+elbo"):
-            self.forward()
-        if fwd_persist:
-            _ext_native().gemm_persist(prev)
-            _ext_native().gemm_grid_reserve(prev_r)
-        with trace_range("flow_backward"):
-            self.backward()
-        if reduce_fn is not None:
-            with trace_range("grad_allreduce_wait"):
-                reduce_fn()
-        with trace_range("optimizer"):
-            self.optimizer_step()
 
     # ------------------------------------------------------------------ inference
     @torch.no_grad()
@@ -681,12 +611,3 @@ class RealNVPVI:
         q = (z0 - mu) * torch.exp(-0.5 * lv)
         lq0 = -0.5 * self.cfg.dim * math.log(2 * math.pi) - 0.5 * lv.sum() - 0.5 * (q * q).sum(1)
         return lq0 + ldj_inv
-
-    def state_dict(self) -> dict:
-        return {"params": self.params.state_dict(), "step": self.step_t.detach().cpu(),
-                "rng_offset": self.rng_offset.detach().cpu(), "cfg": self.cfg.__dict__}
-
-    def load_state_dict(self, sd: dict) -> None:
-        self.params.load_state_dict(sd["params"])
-        self.step_t.copy_(sd["step"])
-        self.rng_offset.copy_(sd["rng_offset"])

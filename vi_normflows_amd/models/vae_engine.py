@@ -28,8 +28,8 @@ import math
 
 import torch
 
-from ..ops import fused
 from ..utils.flat import FlatLayout, FlatParams
+from .engine_core import FlatEngine, anneal_beta
 from .vae import PlanarVAE, VAEConfig
 
 _H = 64
@@ -40,7 +40,7 @@ def _mlp_names(prefix: str, L: int):
             + [f"{prefix}.Wo", f"{prefix}.bo"])
 
 
-class PlanarVAEEngine:
+class PlanarVAEEngine(FlatEngine):
     """Flat-buffer planar-flow VAE trainer (GPU: two-launch HIP step + fused Adam)."""
 
     def __init__(self, cfg: VAEConfig | None = None, batch: int = 128, device="cuda",
@@ -56,9 +56,7 @@ class PlanarVAEEngine:
         self.B = int(batch)
         self.device = torch.device(device)
         self.seed = int(seed)
-        # update rule: adam | rmsprop | sgd | rmsprop_momentum (fused flat kernel, optim.hip)
-        self.opt = fused.resolve_optimizer(optimizer, betas, eps)
-        self.lr, self.betas, self.eps = lr, (self.opt.b1, self.opt.b2), self.opt.eps
+        self._init_core(optimizer, betas, eps, lr)
         self.anneal, self.anneal_iters = anneal, anneal_iters
         dz, K, L, Din = cfg.dim_z, cfg.K, cfg.hidden_layers, cfg.dim_x
         self.De = 2 * dz + 2 * dz * K + K
@@ -72,26 +70,13 @@ class PlanarVAEEngine:
             layout.add_unit(ts)
         self.layout = layout
         self.params = FlatParams(layout, self.device, torch.float32)
-        self.params.v_init = self.opt.v_init
+        self._alloc_state()
         self.params.reset_optimizer_state()
         self.offs = [layout.slots[n].offset for n in _mlp_names("enc", L) + _mlp_names("dec", L)]
         dev = self.device
         self.x = torch.zeros(self.B, Din, device=dev)
-        self.step_t = torch.zeros((), device=dev)
-        self.rng_offset = torch.zeros((), dtype=torch.int64, device=dev)
         self.beta = torch.ones((), device=dev)
-        self.loss = torch.zeros((), device=dev)
         self.frow = torch.zeros(self.B, device=dev)
-        self.gnorm2 = torch.zeros((), device=dev)
-        self.skip = torch.zeros((), device=dev)
-        self.gscale = torch.ones((), device=dev)
-        self._partials = torch.zeros(512, device=dev)
-        self.n_skipped = torch.zeros((), device=dev)
-        # DP runner contract (parallel/runner.py): the step's gradients are final after the one
-        # vae_step launch pair, so every unit is handed to the bucketed all-reduce at once;
-        # grad_scale_host folds the 1/world average into the optimizer's gradient multiplier
-        self.unit_ready_hook = None
-        self.grad_scale_host = 1.0
         ldg = (self.De + 3) // 4 * 4   # gphi rows padded to 16 B (vae.hip wgrad float4 loads)
         self.ws = torch.zeros(4 * L * self.B * _H + self.B * (ldg + dz + Din), device=dev)
         self.eps_override = None
@@ -128,30 +113,23 @@ class PlanarVAEEngine:
         self.x.copy_(x)
 
     # ------------------------------------------------------------------ checkpoint
-    def state_dict(self) -> dict:
-        """Parameters + Adam moments, step and the RNG counter (utils.checkpoint.save_engine);
-        beta is a function of the step. The batch is the caller's (set_batch), so a resumed run
-        replays the same batches by iterating its data from the restored step."""
-        return {"params": self.params.state_dict(), "step": self.step_t.detach().cpu(),
-                "rng_offset": self.rng_offset.detach().cpu(),
-                "cfg": {k: v for k, v in self.cfg.__dict__.items()
-                        if isinstance(v, (int, float, str, bool))}}
+    # The state dict (FlatEngine) holds parameters + optimizer moments, step and the RNG counter;
+    # beta is a function of the step. The batch is the caller's (set_batch), so a resumed run
+    # replays the same batches by iterating its data from the restored step.
+    def _cfg_state(self) -> dict:
+        return {k: v for k, v in self.cfg.__dict__.items()
+                if isinstance(v, (int, float, str, bool))}
 
-    def load_state_dict(self, sd: dict) -> None:
-        self.params.load_state_dict(sd["params"])
-        self.step_t.copy_(sd["step"])
-        self.rng_offset.copy_(sd["rng_offset"])
+    def _set_beta(self) -> None:
         if self.anneal == "reference":
-            cool = min(self.anneal_iters / 4.0, 1e4)
-            torch.clamp((self.step_t - 1.0) * (1.0 / cool) + 0.001, max=1.0, out=self.beta)
+            anneal_beta("reference", self.step_t, self.anneal_iters, self.beta)
+
+    _post_load = _set_beta
 
     # ------------------------------------------------------------------ step
     def _update_schedule(self):
-        self.step_t.add_(1.0)
-        self.rng_offset.add_(1)
-        if self.anneal == "reference":   # beta_t = min(1, 0.001 + t / min(max_iter/4, 1e4))
-            cool = min(self.anneal_iters / 4.0, 1e4)
-            torch.clamp((self.step_t - 1.0) * (1.0 / cool) + 0.001, max=1.0, out=self.beta)
+        self._advance()
+        self._set_beta()
 
     def forward_backward(self):
         """Loss into ``self.loss`` and every parameter gradient into the flat grad buffer."""
@@ -223,25 +201,14 @@ class PlanarVAEEngine:
 
         return int(native().vae_rows_lds_bytes(Din, dz, K)) <= 163840
 
-    def optimizer_step(self):
-        P = self.params
-        fused.sumsq_guard(P.grad, self._partials, out_sumsq=self.gnorm2, skip=self.skip,
-                          scale=self.gscale, max_norm=0.0, base_scale=self.grad_scale_host)
-        b1, b2 = self.betas
-        fused.flat_optimizer(self.opt.kind, P.master, P.grad, P.m, P.v, pbf=None, lr=self.lr,
-                             b1=b1, b2=b2, eps=self.eps, wd=0.0, step=self.step_t,
-                             gscale=self.gscale, skip=self.skip)
-        self.n_skipped.add_(self.skip)
-
-    def train_step(self, reduce_fn=None):
-        self._update_schedule()
+    # FlatEngine.train_step: the step's gradients are final after the one vae_step launch pair,
+    # so the "backward" only hands every unit to the bucketed all-reduce, last to first
+    def forward(self):
         self.forward_backward()
-        if self.unit_ready_hook is not None:
-            for u in range(len(self.layout.unit_ranges) - 1, -1, -1):
-                self.unit_ready_hook(u)
-        if reduce_fn is not None:
-            reduce_fn()
-        self.optimizer_step()
+
+    def backward(self):
+        for u in range(len(self.layout.unit_ranges) - 1, -1, -1):
+            self._mark_ready(u)
 
     def capture(self, warmup: int = 2):
         """Capture one train_step into a hipGraph (static x buffer: refill it with set_batch)."""

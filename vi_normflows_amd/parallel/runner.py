@@ -105,11 +105,11 @@ class DataParallelRunner:
             # multi-rank: RCCL kernels run on CUs beside the backward's GEMMs; a persistent GEMM
             # grid (one block per CU, each owning a fixed tile list) would wait for every CU an
             # all-reduce holds, so the backward's products launch one block per tile. The
-            # forward has no collective in flight: engines that support it run the full
-            # persistent grid there (``persist_forward_only``).
+            # forward has no collective in flight: engines whose forward supports it
+            # (``FlatEngine.supports_forward_persist``) run the full persistent grid there.
             _policy_acquire(2 if persist == "dyn" else 0)
             self._policy_held = True
-            if persist in ("fwd", "dyn") and hasattr(engine, "persist_forward_only"):
+            if persist in ("fwd", "dyn") and engine.supports_forward_persist:
                 engine.persist_forward_only = True
         if info.world > 1 or (force and dist.is_initialized()):
             P = engine.params
@@ -163,8 +163,7 @@ class DataParallelRunner:
         if self._policy_held:
             self._policy_held = False
             _policy_release()
-        if hasattr(self.engine, "persist_forward_only"):
-            self.engine.persist_forward_only = False
+        self.engine.persist_forward_only = False
 
     def __enter__(self):
         return self

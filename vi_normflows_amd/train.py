@@ -15,7 +15,6 @@ import argparse
 import contextlib
 import functools
 import json
-import math
 import os
 import time
 from pathlib import Path
@@ -64,6 +63,41 @@ def _runner(eng, info, **kw):
     return _RUNNER_STACKS[-1].enter_context(DataParallelRunner(eng, info, **kw))
 
 
+def _engine_loop(cfg, out, info, logger, eng, record) -> None:
+    """The checkpointed training loop of the RealNVP and MAF engines: resume (extra.resume, or
+    the run's own last checkpoint), hipGraph capture, ``cfg.iters`` steps with fault injection,
+    logging (``record(samples_per_s)``: the log line without its step) and checkpoints."""
+    from .utils.checkpoint import load_engine, save_engine
+
+    ckpt = out / "ckpt.pt"
+    if cfg.extra.get("resume"):
+        load_engine(eng, cfg.extra["resume"], info.rank)
+    elif cfg.extra.get("auto_resume", True) and ckpt.exists():
+        # elastic-lite: a job restarted by torchrun --max-restarts continues from its last
+        # checkpoint (every rank reads the shared state + its own RNG stream and rank-local
+        # state, e.g. the MAF engine's delayed e4m3 scales)
+        load_engine(eng, ckpt, info.rank)
+        if info.is_main:
+            print(f"[train] resumed from {ckpt} at step {int(eng.step_t.item())}", flush=True)
+    run = _runner(eng, info)
+    fault = bool(os.environ.get("VINF_FAULT"))
+    if eng.device.type == "cuda" and cfg.extra.get("graph", True) and not fault:
+        run.capture(warmup=1)
+    t0 = time.perf_counter()
+    start = int(eng.step_t.item())
+    for t in range(start, cfg.iters):
+        maybe_inject(t, info.rank)
+        run.step()
+        if t == start or t % cfg.log_every == 0 or t == cfg.iters - 1:   # first step logged too
+            el = time.perf_counter() - t0
+            logger.log({"step": t, **record((t - start + 1) * cfg.batch * info.world / el)})
+        if cfg.ckpt_every and (t + 1) % cfg.ckpt_every == 0:
+            save_engine(eng, ckpt, info.rank)
+            vdist.barrier()   # the checkpoint is complete on every rank before anyone moves on
+    save_engine(eng, ckpt, info.rank)
+    vdist.barrier()
+
+
 def run_flow_vi(cfg, out, info, logger):
     from .inference.flow_vi import fit_flow_vi
     from .viz.plots import plot_density_and_samples, plot_loss
@@ -91,8 +125,6 @@ def run_flow_vi(cfg, out, info, logger):
 @_closes_runners
 def run_realnvp(cfg, out, info, logger):
     from .models.realnvp import RealNVPConfig, RealNVPVI
-    from .parallel.runner import DataParallelRunner
-    from .utils.checkpoint import load_engine, save_engine
 
     dev = _device(cfg, info)
     if cfg.schedule not in ("reference", "none"):
@@ -105,36 +137,9 @@ def run_realnvp(cfg, out, info, logger):
     eng = RealNVPVI(rc, batch=cfg.batch, device=dev, seed=cfg.seed, rank=info.rank, lr=cfg.lr,
                     lr_warmup=cfg.lr_warmup, max_grad_norm=cfg.max_grad_norm,
                     optimizer=cfg.optimizer)
-    ckpt = out / "ckpt.pt"
-    if cfg.extra.get("resume"):
-        load_engine(eng, cfg.extra["resume"], info.rank)
-    elif cfg.extra.get("auto_resume", True) and ckpt.exists():
-        # elastic-lite: a job restarted by torchrun --max-restarts continues from its last
-        # checkpoint (every rank reads the shared state + its own RNG stream)
-        load_engine(eng, ckpt, info.rank)
-        if info.is_main:
-            print(f"[train] resumed from {ckpt} at step {int(eng.step_t.item())}", flush=True)
-    run = _runner(eng, info)
-    fault = bool(os.environ.get("VINF_FAULT"))
-    if dev.type == "cuda" and cfg.extra.get("graph", True) and not fault:
-        run.capture(warmup=1)
-    t0 = time.perf_counter()
-    start = int(eng.step_t.item())
-    for t in range(start, cfg.iters):
-        maybe_inject(t, info.rank)
-        run.step()
-        if t == start or t % cfg.log_every == 0 or t == cfg.iters - 1:   # first step logged too
-            F = float(eng.loss.item())
-            el = time.perf_counter() - t0
-            logger.log({"step": t, "F": F, "beta": float(eng.beta.item()),
-                        "grad_norm": math.sqrt(max(float(eng.gnorm2.item()), 0.0)),
-                        "skipped": float(eng.n_skipped.item()),
-                        "samples_per_s": (t - start + 1) * cfg.batch * info.world / el})
-        if cfg.ckpt_every and (t + 1) % cfg.ckpt_every == 0:
-            save_engine(eng, ckpt, info.rank)
-            vdist.barrier()   # the checkpoint is complete on every rank before anyone moves on
-    save_engine(eng, ckpt, info.rank)
-    vdist.barrier()
+    _engine_loop(cfg, out, info, logger, eng, lambda sps: {
+        "F": float(eng.loss.item()), "beta": float(eng.beta.item()), **eng.log_record(),
+        "samples_per_s": sps})
     return {"free_energy": float(eng.loss.item()), "steps": cfg.iters,
             "skipped_steps": float(eng.n_skipped.item())}
 
@@ -189,8 +194,6 @@ def run_planar_vae(cfg, out, info, logger):
         # models/vae_engine.py: the whole step in two HIP launches + flat Adam, one hipGraph; DP
         # through the runner (rank 0's weights broadcast, bucketed RCCL all-reduce, 1/world in
         # the optimizer); rank-distinct noise streams come from the rank seed
-        from .parallel.runner import DataParallelRunner
-
         eng = PlanarVAEEngine(vcfg, batch=cfg.batch, device=dev, seed=rank_seed(cfg.seed, info.rank),
                               lr=cfg.lr, anneal=cfg.schedule, anneal_iters=cfg.iters,
                               optimizer=cfg.optimizer)
@@ -204,10 +207,8 @@ def run_planar_vae(cfg, out, info, logger):
         run = _runner(eng, info)
         if dev.type == "cuda" and cfg.extra.get("graph", True):
             run.capture(warmup=1)
-        eng.params.reset_optimizer_state()   # the capture warm-up stepped the optimizer
+        eng.reset_after_warmup()   # the capture warm-up stepped the optimizer and the schedule
         eng.load_module(vae)
-        eng.step_t.zero_()
-        eng.n_skipped.zero_()
         recon_every = int(cfg.extra.get("recon_every", 200))
         x_probe = X[min(101, X.shape[0] - 1)]          # the reference plots X[101] (utils.py:33)
         F = float("nan")
@@ -221,9 +222,7 @@ def run_planar_vae(cfg, out, info, logger):
                 F = eng.loss.item()
                 if logger is not None:
                     logger.log({"step": t + 1, "F": F, "beta": eng.beta.item(), "path": "engine",
-                                "optimizer": eng.opt.name,
-                                "grad_norm": math.sqrt(max(float(eng.gnorm2.item()), 0.0)),
-                                "skipped": float(eng.n_skipped.item())})
+                                "optimizer": eng.opt.name, **eng.log_record()})
             if info.is_main and recon_every > 0 and ((t + 1) % recon_every == 0 or last):
                 # optimization.py:103-111: a true-vs-reconstruction figure every 200 steps
                 from .viz.plots import compare_reconstruction
@@ -275,7 +274,6 @@ def run_iaf_vae(cfg, out, info, logger):
         # models/iaf_engine.py: flat buffers, explicit backward, one hipGraph (DP: the runner's
         # bucketed all-reduce; rank 0's parameters are broadcast)
         from .models.iaf_engine import IAFEngine
-        from .parallel.runner import DataParallelRunner
         from .utils.checkpoint import save_engine
 
         eng = IAFEngine(icfg, cfg.batch, X[:nb * cfg.batch].reshape(nb * cfg.batch, -1),
@@ -286,18 +284,14 @@ def run_iaf_vae(cfg, out, info, logger):
         if cfg.extra.get("graph", True):
             run.capture(warmup=1)
             eng.load_module(model)     # the capture warm-up stepped Adam: start from the init
-            eng.params.reset_optimizer_state()
-            eng.step_t.zero_()         # ... and advanced the schedule: beta_t restarts at t = 0
-            eng.n_skipped.zero_()
+            eng.reset_after_warmup()   # ... and advanced the schedule: beta_t restarts at t = 0
         t0 = time.perf_counter()
         for t in range(cfg.iters):
             run.step()
             if t % cfg.log_every == 0 or t == cfg.iters - 1:
                 F = float(eng.loss.item())
                 logger.log({"step": t, "F": F, "beta": float(eng.beta_t.item()), "path": "engine",
-                            "optimizer": eng.opt.name,
-                            "grad_norm": math.sqrt(max(float(eng.gnorm2.item()), 0.0)),
-                            "skipped": float(eng.n_skipped.item()),
+                            "optimizer": eng.opt.name, **eng.log_record(),
                             "samples_per_s": (t + 1) * cfg.batch * info.world
                             / (time.perf_counter() - t0)})
         save_engine(eng, out / "ckpt.pt", info.rank)
@@ -323,42 +317,14 @@ def run_maf(cfg, out, info, logger):
     dev = _device(cfg, info)
     if cfg.extra.get("impl", "engine") == "engine":
         from .models.maf_engine import MAFEngine, MAFEngineConfig
-        from .parallel.runner import DataParallelRunner
-        from .utils.checkpoint import load_engine, save_engine
 
         mc = MAFEngineConfig(dim=cfg.dim, n_layers=cfg.K, hidden=cfg.hidden,
                              precision=cfg.extra.get("precision", "fp8"))
         eng = MAFEngine(mc, batch=cfg.batch, device=dev, seed=cfg.seed, rank=info.rank, lr=cfg.lr,
                         optimizer=cfg.optimizer)
-        ckpt = out / "ckpt.pt"
-        # elastic-lite as in run_realnvp; every rank also restores its own delayed e4m3 scales
-        # (MAFEngine.rank_state_dict) from its per-rank file
-        if cfg.extra.get("resume"):
-            load_engine(eng, cfg.extra["resume"], info.rank)
-        elif cfg.extra.get("auto_resume", True) and ckpt.exists():
-            load_engine(eng, ckpt, info.rank)
-            if info.is_main:
-                print(f"[train] resumed from {ckpt} at step {int(eng.step_t.item())}", flush=True)
-        run = _runner(eng, info)
-        fault = bool(os.environ.get("VINF_FAULT"))
-        if dev.type == "cuda" and cfg.extra.get("graph", True) and not fault:
-            run.capture(warmup=1)
-        t0 = time.perf_counter()
-        start = int(eng.step_t.item())
-        for t in range(start, cfg.iters):
-            maybe_inject(t, info.rank)
-            run.step()
-            if t == start or t % cfg.log_every == 0 or t == cfg.iters - 1:
-                el = time.perf_counter() - t0
-                logger.log({"step": t, "nll": float(eng.loss.item()),
-                            "grad_norm": math.sqrt(max(float(eng.gnorm2.item()), 0.0)),
-                            "samples_per_s": (t - start + 1) * cfg.batch * info.world / el,
-                            **eng.fp8_saturation()})
-            if cfg.ckpt_every and (t + 1) % cfg.ckpt_every == 0:
-                save_engine(eng, ckpt, info.rank)
-                vdist.barrier()
-        save_engine(eng, ckpt, info.rank)
-        vdist.barrier()
+        _engine_loop(cfg, out, info, logger, eng, lambda sps: {
+            "nll": float(eng.loss.item()), "grad_norm": eng.log_record()["grad_norm"],
+            "samples_per_s": sps, **eng.fp8_saturation()})
         return {"nll": float(eng.loss.item()), "nll_floor_entropy": mc.entropy(),
                 "precision": mc.precision if dev.type == "cuda" else "fp32"}
 

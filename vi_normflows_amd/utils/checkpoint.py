@@ -38,9 +38,8 @@ def save_engine(engine, path, rank: int = 0, extra: dict | None = None) -> None:
         if extra:
             payload["extra"] = extra
         atomic_save(payload, path)
-    local = engine.rank_state_dict() if hasattr(engine, "rank_state_dict") else {}
     atomic_save({"rng_offset": sd["rng_offset"], "rank": rank, "step": sd.get("step"),
-                 "torch_rng": torch.get_rng_state(), "rank_state": local},
+                 "torch_rng": torch.get_rng_state(), "rank_state": engine.rank_state_dict()},
                 f"{path}.rank{rank}.rng")
 
 
@@ -58,7 +57,7 @@ def load_engine(engine, path, rank: int = 0) -> dict:
                                                               torch.as_tensor(st).cpu()):
             engine.rng_offset.copy_(r["rng_offset"])
             torch.set_rng_state(r["torch_rng"])
-            if r.get("rank_state") and hasattr(engine, "load_rank_state_dict"):
+            if r.get("rank_state"):
                 engine.load_rank_state_dict(r["rank_state"])
     return payload.get("extra", {})
 
