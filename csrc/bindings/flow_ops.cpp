@@ -1,13 +1,11 @@
 // TORCH_LIBRARY fragment for the fused planar / radial stacks.
 #include <torch/library.h>
 #include <ATen/ATen.h>
-#include <c10/hip/HIPStream.h>
 
+#include "bind_common.h"
 #include "launchers.h"
 
 namespace {
-
-hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
 void chk(const at::Tensor& t, const char* n) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous(), n,

@@ -2,16 +2,14 @@
 #include <vector>
 #include <torch/library.h>
 #include <ATen/ATen.h>
-#include <c10/hip/HIPStream.h>
 
 #include <cstdlib>
 
+#include "bind_common.h"
 #include "launchers.h"
 #include "nf_common.h"
 
 namespace {
-
-hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
 long ld2(const at::Tensor& t) { return t.size(0) <= 1 ? t.size(1) : t.stride(0); }
 

@@ -7,13 +7,13 @@
 // as plain C launchers declared in launchers.h.
 #include <torch/library.h>
 #include <ATen/ATen.h>
-#include <c10/hip/HIPStream.h>
 #include <c10/hip/HIPGuard.h>
 
 #include <sstream>
 #include <vector>
 #include <stdexcept>
 
+#include "bind_common.h"
 #include "launchers.h"
 
 void nf_throw_hip_error(hipError_t e, const char* expr, const char* file, int line) {
@@ -23,8 +23,6 @@ void nf_throw_hip_error(hipError_t e, const char* expr, const char* file, int li
 }
 
 namespace {
-
-hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
 void check_cuda(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");

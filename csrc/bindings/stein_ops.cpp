@@ -2,13 +2,11 @@
 // row sums of the Stein kernel matrix. Neither op is differentiable.
 #include <torch/library.h>
 #include <ATen/ATen.h>
-#include <c10/hip/HIPStream.h>
 
+#include "bind_common.h"
 #include "launchers.h"
 
 namespace {
-
-hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
 constexpr int64_t kMaxDim = 64;
 constexpr int64_t kMaxSplits = 65535;   // gridDim.y

@@ -1,15 +1,13 @@
 // TORCH_LIBRARY fragment for the fused Sylvester flow stack (sylvester.hip).
 #include <torch/library.h>
 #include <ATen/ATen.h>
-#include <c10/hip/HIPStream.h>
 
 #include <vector>
 
+#include "bind_common.h"
 #include "launchers.h"
 
 namespace {
-
-hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
 void chk_dense(const at::Tensor& t, const char* n, at::IntArrayRef sizes) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous(), "sylvester: ", n,

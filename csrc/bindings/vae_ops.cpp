@@ -1,8 +1,8 @@
 // TORCH_LIBRARY fragment for the planar-flow VAE step (csrc/kernels/vae.hip).
 #include <torch/library.h>
 #include <ATen/ATen.h>
-#include <c10/hip/HIPStream.h>
 
+#include "bind_common.h"
 #include "launchers.h"
 
 namespace {
@@ -102,7 +102,7 @@ void vae_step(const at::Tensor& master, const at::Tensor& grad, at::IntArrayRef 
                      beta.data_ptr<float>(), (int)B, (int)Din, (int)dz, (int)K, (int)L, eact,
                      egrad, gphi, zk, dact, dgrad, dl, frow.data_ptr<float>(),
                      loss.data_ptr<float>(), zk_p, ldj_p, grd,
-                     c10::hip::getCurrentHIPStream().stream());
+                     cur_stream());
 }
 
 }  // namespace

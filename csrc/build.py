@@ -44,7 +44,7 @@ def _torch_paths():
 
 
 def _headers() -> list[Path]:
-    return sorted((CSRC / "include").glob("*.h"))
+    return sorted([*(CSRC / "include").glob("*.h"), *(CSRC / "bindings").glob("*.h")])
 
 
 def _stale(obj: Path, src: Path, deps: list[Path]) -> bool:

@@ -22,24 +22,10 @@
 // The backward saves nothing: it recomputes the bin from params and the input-side value, in
 // both directions, and one body serves both because x = f^-1(y) gives dx/dy = 1 / y',
 // dx/dp = -f_p / y' and ldj_inv = -L(x, p) with the same partials f_p, y', L_x, L_p.
-#include "nf_common.h"
-
-#include <math.h>
-
-// The element math is __host__ __device__ so it can also be exercised by a host program; the
-// fast intrinsics exist on the device only.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define RQS_EXP(v) __expf(v)
-#define RQS_LOG(v) __logf(v)
-#define RQS_RCP(v) __builtin_amdgcn_rcpf(v)
-#define RQS_SQRT(v) __builtin_amdgcn_sqrtf(v)
-#else
-#define RQS_EXP(v) expf(v)
-#define RQS_LOG(v) logf(v)
-#define RQS_RCP(v) (1.0f / (v))
-#define RQS_SQRT(v) sqrtf(v)
-#endif
-#define RQS_HD __host__ __device__ __forceinline__
+//
+// The kernels, the row accessors, the fast-math macros and the launch dispatch are the shared
+// element-wise frame of elementwise_flow.h; this file holds the element mathematics and its Op.
+#include "elementwise_flow.h"
 
 namespace nf {
 
@@ -47,30 +33,16 @@ constexpr float RQS_MIN = 1e-3f;            // min_w = min_h = min_d
 constexpr float RQS_C0 = 0.539742417236952f;  // log(expm1(1 - min_d)): ud = 0 gives d = 1
 constexpr float RQS_Q = 0.631752495386337f;   // 1 - exp(-(1 - min_d)) = sigmoid(c0)
 
-// Accesses inside a params row are (wave-uniform row pointer)[32-bit column]; the column walks
-// plane by plane (+= Dh), so no per-plane address is kept live across the loop over j.
-RQS_HD float rqs_ld(const float* p, unsigned j) { return p[j]; }
-RQS_HD float rqs_ld(const bf16_t* p, unsigned j) {
-  union { uint32_t u; float f; } c;
-  c.u = ((uint32_t)p[j]) << 16;
-  return c.f;
-}
-RQS_HD void rqs_st(float* p, unsigned j, float v) { p[j] = v; }
-RQS_HD void rqs_st(bf16_t* p, unsigned j, float v) {
-  const __hip_bfloat16 h = __float2bfloat16(v);
-  p[j] = *reinterpret_cast<const bf16_t*>(&h);
-}
-
 // Interior derivative d = min_d + softplus(ud + c0). Around ud = 0 it is evaluated as the equal
 // 1 + log((1 - q) + q e^ud), which is exactly 1 at ud = 0 (q + (1 - q) == 1 in fp32, exp(0) == 1,
 // log(1) == 0, with the fast intrinsics too): a d one ulp off 1 rounds every element's
 // log dy/dx of the identity spline the same way, and the row sum drifts by Dh ulp. Its absolute
 // error (~1e-7) would be a relative one where d approaches min_d, so far below 0 (rare) the
 // literal form with the precise log1p is used.
-RQS_HD float rqs_deriv(float ud) {
-  if (ud > -2.0f && ud < 15.0f) return 1.0f + RQS_LOG(fmaf(RQS_Q, RQS_EXP(ud), 1.0f - RQS_Q));
+EW_HD float rqs_deriv(float ud) {
+  if (ud > -2.0f && ud < 15.0f) return 1.0f + EW_LOG(fmaf(RQS_Q, EW_EXP(ud), 1.0f - RQS_Q));
   const float t = ud + RQS_C0;
-  return RQS_MIN + (t > 20.f ? t : log1pf(RQS_EXP(t)));
+  return RQS_MIN + (t > 20.f ? t : log1pf(EW_EXP(t)));
 }
 
 // The bin that holds one element, and what the backward needs of the two softmaxes.
@@ -87,15 +59,15 @@ struct RqsBin {
 // softmaxes in smw / smh (0 for k >= K) and picks the bin of v: by the x-knots, or by the
 // y-knots for the inverse. The knots are running sums from -bound, as in the composite.
 template <int KMAX, bool INVERSE, typename TP>
-RQS_HD void rqs_find_bin(const TP* __restrict__ pr, unsigned j, unsigned Dh, int K, float bound,
-                         float v, float (&smw)[KMAX], float (&smh)[KMAX], RqsBin& bn) {
+EW_HD void rqs_find_bin(const TP* __restrict__ pr, unsigned j, unsigned Dh, int K, float bound,
+                        float v, float (&smw)[KMAX], float (&smh)[KMAX], RqsBin& bn) {
   // all 2K loads are issued before the first use; the column offset walks plane by plane
   unsigned ow = j, oh = j + (unsigned)K * Dh;
 #pragma unroll
   for (int k = 0; k < KMAX; ++k) {
     if (k < K) {
-      smw[k] = rqs_ld(pr, ow);
-      smh[k] = rqs_ld(pr, oh);
+      smw[k] = ew_ld(pr, ow);
+      smh[k] = ew_ld(pr, oh);
       ow += Dh;
       oh += Dh;
     } else {
@@ -115,13 +87,13 @@ RQS_HD void rqs_find_bin(const TP* __restrict__ pr, unsigned j, unsigned Dh, int
 #pragma unroll
   for (int k = 0; k < KMAX; ++k) {
     if (k < K) {
-      smw[k] = RQS_EXP(smw[k] - mw);
-      smh[k] = RQS_EXP(smh[k] - mh);
+      smw[k] = EW_EXP(smw[k] - mw);
+      smh[k] = EW_EXP(smh[k] - mh);
       sw += smw[k];
       sh += smh[k];
     }
   }
-  const float iw = RQS_RCP(sw), ih = RQS_RCP(sh);
+  const float iw = EW_RCP(sw), ih = EW_RCP(sh);
   const float c2 = 2.0f * bound, cm = 1.0f - (float)K * RQS_MIN;
   float kx = -bound, ky = -bound, cw = 0.f, ch = 0.f;
   bn.k = 0;
@@ -153,8 +125,8 @@ RQS_HD void rqs_find_bin(const TP* __restrict__ pr, unsigned j, unsigned Dh, int
   bn.h = c2 * fmaf(cm, bn.sh, RQS_MIN);
   // end knots have derivative 1; the index is clamped so the gather stays inside the planes
   const bool first = bn.k == 0, last = bn.k == K - 1;
-  const float ud0 = rqs_ld(pr, (unsigned)(2 * K + (first ? 0 : bn.k - 1)) * Dh + j);
-  const float ud1 = rqs_ld(pr, (unsigned)(2 * K + (last ? K - 2 : bn.k)) * Dh + j);
+  const float ud0 = ew_ld(pr, (unsigned)(2 * K + (first ? 0 : bn.k - 1)) * Dh + j);
+  const float ud1 = ew_ld(pr, (unsigned)(2 * K + (last ? K - 2 : bn.k)) * Dh + j);
   bn.u0 = ud0 + RQS_C0;
   bn.u1 = ud1 + RQS_C0;
   bn.d0 = first ? 1.0f : rqs_deriv(ud0);
@@ -169,8 +141,8 @@ struct RqsEval {
 };
 
 template <bool INVERSE>
-RQS_HD void rqs_eval(const RqsBin& bn, float v, RqsEval& ev) {
-  ev.rw = RQS_RCP(bn.w);
+EW_HD void rqs_eval(const RqsBin& bn, float v, RqsEval& ev) {
+  ev.rw = EW_RCP(bn.w);
   ev.s = bn.h / bn.w;
   ev.e = bn.d1 + bn.d0 - 2.0f * ev.s;
   if (INVERSE) {
@@ -179,42 +151,17 @@ RQS_HD void rqs_eval(const RqsBin& bn, float v, RqsEval& ev) {
     const float b = fmaf(bn.h, bn.d0, -dl * ev.e);
     const float c = -ev.s * dl;
     const float disc = fmaxf(fmaf(b, b, -4.0f * a * c), 0.f);
-    ev.th = 2.0f * c * RQS_RCP(-b - RQS_SQRT(disc));
+    ev.th = 2.0f * c * EW_RCP(-b - EW_SQRT(disc));
   } else {
     ev.th = (v - bn.xk) * ev.rw;
   }
   ev.t1 = ev.th * (1.0f - ev.th);
   ev.den = fmaf(ev.e, ev.t1, ev.s);
-  ev.rden = RQS_RCP(ev.den);
+  ev.rden = EW_RCP(ev.den);
   // P = d1 th^2 + 2 s th (1 - th) + d0 (1 - th)^2 as s + (d1 - s) th^2 + (d0 - s) (1 - th)^2:
   // with d0 = d1 = s (the identity spline) P, den and log dy/dx are exact
   const float om = 1.0f - ev.th;
   ev.P = fmaf(bn.d1 - ev.s, ev.th * ev.th, fmaf(bn.d0 - ev.s, om * om, ev.s));
-}
-
-// One element of the forward / inverse transform; returns the output and adds log dy/dx
-// (inverse: minus it) to acc.
-template <int KMAX, bool INVERSE, typename TP>
-RQS_HD float rqs_fwd_elem(const TP* __restrict__ pr, unsigned j, unsigned Dh, int K, float bound,
-                          float v, float& acc) {
-  if (!(v > -bound && v < bound)) return v;   // linear tails (and NaN): identity, ldj 0
-  float smw[KMAX], smh[KMAX];
-  RqsBin bn;
-  rqs_find_bin<KMAX, INVERSE>(pr, j, Dh, K, bound, v, smw, smh, bn);
-  RqsEval ev;
-  rqs_eval<INVERSE>(bn, v, ev);
-  const float ypr = ev.s * ev.s * ev.P * ev.rden * ev.rden;   // dy/dx
-  const float L = RQS_LOG(ypr);
-  float out;
-  if (INVERSE) {
-    out = fmaf(ev.th, bn.w, bn.xk);
-    acc -= L;
-  } else {
-    // s th^2 + d0 th (1 - th) = th (d0 + (s - d0) th)
-    out = fmaf(bn.h * ev.th * fmaf(ev.s - bn.d0, ev.th, bn.d0), ev.rden, bn.yk);
-    acc += L;
-  }
-  return out;
 }
 
 // Gradients of one element. With theta = (x - xk) / w, s = h / w, t1 = theta (1 - theta),
@@ -229,9 +176,9 @@ struct RqsGrad {
 };
 
 template <bool INVERSE>
-RQS_HD void rqs_grad_elem(const RqsBin& bn, const RqsEval& ev, int K, float g, float gl,
-                          RqsGrad& gr) {
-  const float th = ev.th, t1 = ev.t1, s = ev.s, rden = ev.rden, rP = RQS_RCP(ev.P);
+EW_HD void rqs_grad_elem(const RqsBin& bn, const RqsEval& ev, int K, float g, float gl,
+                         RqsGrad& gr) {
+  const float th = ev.th, t1 = ev.t1, s = ev.s, rden = ev.rden, rP = EW_RCP(ev.P);
   const float om = 1.0f - th, om2 = 1.0f - 2.0f * th;
   const float N = th * fmaf(s - bn.d0, th, bn.d0);
   const float hr2 = bn.h * rden * rden;
@@ -239,7 +186,7 @@ RQS_HD void rqs_grad_elem(const RqsBin& bn, const RqsEval& ev, int K, float g, f
   // partials of L
   const float P_th = 2.0f * (bn.d1 * th + s * om2 - bn.d0 * om);
   const float L_th = P_th * rP - 2.0f * ev.e * om2 * rden;
-  const float L_s = 2.0f * RQS_RCP(s) + 2.0f * t1 * rP - 2.0f * (1.0f - 2.0f * t1) * rden;
+  const float L_s = 2.0f * EW_RCP(s) + 2.0f * t1 * rP - 2.0f * (1.0f - 2.0f * t1) * rden;
   const float L_d0 = om * om * rP - 2.0f * t1 * rden;
   const float L_d1 = th * th * rP - 2.0f * t1 * rden;
   // partials of y
@@ -250,7 +197,7 @@ RQS_HD void rqs_grad_elem(const RqsBin& bn, const RqsEval& ev, int K, float g, f
   const float y_d1 = -hr2 * N * t1;
   float ge = g, le = gl;
   if (INVERSE) {
-    ge = -(g - gl * L_th * ev.rw) * RQS_RCP(ypr);
+    ge = -(g - gl * L_th * ev.rw) * EW_RCP(ypr);
     le = -gl;
   }
   const float A_th = ge * y_th + le * L_th;
@@ -261,171 +208,108 @@ RQS_HD void rqs_grad_elem(const RqsBin& bn, const RqsEval& ev, int K, float g, f
   gr.Gh = ge * y_h + A_s * ev.rw;
   gr.Gyk = ge;
   // d = min_d + softplus(u): dd/dud = sigmoid(u)
-  const float sg0 = RQS_RCP(1.0f + RQS_EXP(-bn.u0)), sg1 = RQS_RCP(1.0f + RQS_EXP(-bn.u1));
+  const float sg0 = EW_RCP(1.0f + EW_EXP(-bn.u0)), sg1 = EW_RCP(1.0f + EW_EXP(-bn.u1));
   gr.gu0 = bn.k == 0 ? 0.f : (ge * y_d0 + le * L_d0) * sg0;
   gr.gu1 = bn.k == K - 1 ? 0.f : (ge * y_d1 + le * L_d1) * sg1;
 }
 
-template <int KMAX, bool INVERSE, typename TP>
-__global__ void __launch_bounds__(256) rqs_fwd_kernel(
-    const TP* __restrict__ params, const float* __restrict__ x, float* __restrict__ y,
-    float* __restrict__ ldj, int B, int Dh, int K, float bound, int ldj_init) {
-  const int lane = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= B) return;
-  const TP* p_r = params + row * (long)(3 * K - 1) * Dh;
-  const float* x_r = x + row * Dh;
-  float* y_r = y + row * Dh;
-  float acc = 0.f;
-#pragma unroll 1
-  for (int j = lane; j < Dh; j += 64)
-    y_r[j] = rqs_fwd_elem<KMAX, INVERSE>(p_r, j, (unsigned)Dh, K, bound, x_r[j], acc);
-  acc = wave_sum(acc);
-  if (lane == 0) ldj[row] = ldj_init ? acc : ldj[row] + acc;
-}
+// The spline as an element-wise Op (elementwise_flow.h): K bins on (-bound, bound). The element
+// functions are its members themselves: a member that only forwarded to a free function would
+// add an inlining layer, and that alone reorders the generated code.
+template <int KMAX, bool INVERSE>
+struct RqsOp {
+  int K;
+  float bound;
+  static constexpr const char* NEED = "2 <= K <= 32, bound > 0";
+  EW_HD bool valid() const { return K >= 2 && K <= 32 && bound > 0.f; }
+  EW_HD int planes() const { return 3 * K - 1; }
 
-// Backward of element j of a row: writes its 3K-1 parameter gradients (dpr = the dparams row)
-// and returns the gradient of the direction's input.
-template <int KMAX, bool INVERSE, typename TP>
-RQS_HD float rqs_bwd_elem(const TP* __restrict__ pr, TP* __restrict__ dpr, unsigned j,
-                          unsigned Dh, int K, float bound, float v, float g, float gl) {
-  if (!(v > -bound && v < bound)) {   // tails: identity, no parameter gradient
-    unsigned o = j;
-    for (int k = 0; k < 3 * K - 1; ++k, o += Dh) rqs_st(dpr, o, 0.f);
-    return g;
-  }
-  float smw[KMAX], smh[KMAX];
-  RqsBin bn;
-  rqs_find_bin<KMAX, INVERSE>(pr, j, Dh, K, bound, v, smw, smh, bn);
-  RqsEval ev;
-  rqs_eval<INVERSE>(bn, v, ev);
-  RqsGrad gr;
-  rqs_grad_elem<INVERSE>(bn, ev, K, g, gl, gr);
-  // A bin's size gets Gw (Gh) if it is the chosen bin and the knot's gradient if it lies
-  // before it; then the softmax Jacobian sm_i (G_i - sum_j G_j sm_j) times d size / d softmax.
-  const float cs = 2.0f * bound * (1.0f - (float)K * RQS_MIN);
-  const float Sw = fmaf(gr.Gw, bn.sw, gr.Gxk * bn.cw);
-  const float Sh = fmaf(gr.Gh, bn.sh, gr.Gyk * bn.ch);
-  unsigned ow = j, oh = j + (unsigned)K * Dh, od = j + 2u * (unsigned)K * Dh;
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k) {
-    if (k < K) {
-      const float Gwk = k == bn.k ? gr.Gw : (k < bn.k ? gr.Gxk : 0.f);
-      const float Ghk = k == bn.k ? gr.Gh : (k < bn.k ? gr.Gyk : 0.f);
-      rqs_st(dpr, ow, cs * smw[k] * (Gwk - Sw));
-      rqs_st(dpr, oh, cs * smh[k] * (Ghk - Sh));
-      ow += Dh;
-      oh += Dh;
+  // One element of the forward / inverse transform; returns the output and adds log dy/dx
+  // (inverse: minus it) to acc.
+  template <typename TP>
+  EW_HD float fwd_elem(const TP* __restrict__ pr, unsigned j, unsigned Dh, float v,
+                       float& acc) const {
+    if (!(v > -bound && v < bound)) return v;   // linear tails (and NaN): identity, ldj 0
+    float smw[KMAX], smh[KMAX];
+    RqsBin bn;
+    rqs_find_bin<KMAX, INVERSE>(pr, j, Dh, K, bound, v, smw, smh, bn);
+    RqsEval ev;
+    rqs_eval<INVERSE>(bn, v, ev);
+    const float ypr = ev.s * ev.s * ev.P * ev.rden * ev.rden;   // dy/dx
+    const float L = EW_LOG(ypr);
+    float out;
+    if (INVERSE) {
+      out = fmaf(ev.th, bn.w, bn.xk);
+      acc -= L;
+    } else {
+      // s th^2 + d0 th (1 - th) = th (d0 + (s - d0) th)
+      out = fmaf(bn.h * ev.th * fmaf(ev.s - bn.d0, ev.th, bn.d0), ev.rden, bn.yk);
+      acc += L;
     }
+    return out;
   }
-#pragma unroll
-  for (int k = 0; k < KMAX - 1; ++k) {
-    if (k < K - 1) {
-      const float gd = k == bn.k - 1 ? gr.gu0 : (k == bn.k ? gr.gu1 : 0.f);
-      rqs_st(dpr, od, gd);
-      od += Dh;
-    }
-  }
-  return gr.gin;
-}
 
-// g_out [B, Dh], g_ldj [B]: upstream gradients of the direction's output and ldj.
-// dparams [B, (3K-1) Dh] in the dtype of params (every column written), gx [B, Dh].
-template <int KMAX, bool INVERSE, typename TP>
-__global__ void __launch_bounds__(256) rqs_bwd_kernel(
-    const TP* __restrict__ params, const float* __restrict__ x, const float* __restrict__ g_out,
-    const float* __restrict__ g_ldj, TP* __restrict__ dparams, float* __restrict__ gx, int B,
-    int Dh, int K, float bound) {
-  const int lane = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= B) return;
-  const long prow = row * (long)(3 * K - 1) * Dh;
-  const float gl = g_ldj[row];
-#pragma unroll 1
-  for (int j = lane; j < Dh; j += 64)
-    gx[row * Dh + j] = rqs_bwd_elem<KMAX, INVERSE>(params + prow, dparams + prow, j,
-                                                   (unsigned)Dh, K, bound, x[row * Dh + j],
-                                                   g_out[row * Dh + j], gl);
-}
+  // Backward of element j of a row: writes its 3K-1 parameter gradients (dpr = the dparams row)
+  // and returns the gradient of the direction's input.
+  template <typename TP>
+  EW_HD float bwd_elem(const TP* __restrict__ pr, TP* __restrict__ dpr, unsigned j, unsigned Dh,
+                       float v, float g, float gl) const {
+    if (!(v > -bound && v < bound)) {   // tails: identity, no parameter gradient
+      unsigned o = j;
+      for (int k = 0; k < 3 * K - 1; ++k, o += Dh) ew_st(dpr, o, 0.f);
+      return g;
+    }
+    float smw[KMAX], smh[KMAX];
+    RqsBin bn;
+    rqs_find_bin<KMAX, INVERSE>(pr, j, Dh, K, bound, v, smw, smh, bn);
+    RqsEval ev;
+    rqs_eval<INVERSE>(bn, v, ev);
+    RqsGrad gr;
+    rqs_grad_elem<INVERSE>(bn, ev, K, g, gl, gr);
+    // A bin's size gets Gw (Gh) if it is the chosen bin and the knot's gradient if it lies
+    // before it; then the softmax Jacobian sm_i (G_i - sum_j G_j sm_j) times d size / d softmax.
+    const float cs = 2.0f * bound * (1.0f - (float)K * RQS_MIN);
+    const float Sw = fmaf(gr.Gw, bn.sw, gr.Gxk * bn.cw);
+    const float Sh = fmaf(gr.Gh, bn.sh, gr.Gyk * bn.ch);
+    unsigned ow = j, oh = j + (unsigned)K * Dh, od = j + 2u * (unsigned)K * Dh;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      if (k < K) {
+        const float Gwk = k == bn.k ? gr.Gw : (k < bn.k ? gr.Gxk : 0.f);
+        const float Ghk = k == bn.k ? gr.Gh : (k < bn.k ? gr.Gyk : 0.f);
+        ew_st(dpr, ow, cs * smw[k] * (Gwk - Sw));
+        ew_st(dpr, oh, cs * smh[k] * (Ghk - Sh));
+        ow += Dh;
+        oh += Dh;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < KMAX - 1; ++k) {
+      if (k < K - 1) {
+        const float gd = k == bn.k - 1 ? gr.gu0 : (k == bn.k ? gr.gu1 : 0.f);
+        ew_st(dpr, od, gd);
+        od += Dh;
+      }
+    }
+    return gr.gin;
+  }
+};
 
 }  // namespace nf
 
 using namespace nf;
 
-// columns inside a params row are 32-bit offsets (byte offsets stay below 2^31)
-static bool rqs_row_fits(int K, int Dh) { return (long)(3 * K - 1) * Dh < (1L << 29); }
-
-#define NF_RQS_KMAX(CALL)        \
-  do {                           \
-    if (K <= 8) { CALL(8); }     \
-    else if (K <= 16) { CALL(16); } \
-    else { CALL(32); }           \
-  } while (0)
-
 void nf_launch_rqs_fwd(const void* params, int params_is_bf16, const float* x, float* y,
                        float* ldj, int B, int Dh, int K, float bound, int inverse, int ldj_init,
                        hipStream_t stream) {
-  if (B <= 0 || Dh <= 0) return;
-  if (K < 2 || K > 32 || !(bound > 0.f) || !rqs_row_fits(K, Dh)) {
-    fprintf(stderr, "rqs_fwd: need 2 <= K <= 32, bound > 0 and (3K-1) Dh < 2^29\n");
-    abort();
-  }
-  dim3 grid((B + 3) / 4), block(256);
-#define NF_RQS_F(KM)                                                                          \
-  do {                                                                                        \
-    if (params_is_bf16) {                                                                     \
-      if (inverse)                                                                            \
-        hipLaunchKernelGGL((rqs_fwd_kernel<KM, true, bf16_t>), grid, block, 0, stream,         \
-                           (const bf16_t*)params, x, y, ldj, B, Dh, K, bound, ldj_init);      \
-      else                                                                                    \
-        hipLaunchKernelGGL((rqs_fwd_kernel<KM, false, bf16_t>), grid, block, 0, stream,        \
-                           (const bf16_t*)params, x, y, ldj, B, Dh, K, bound, ldj_init);      \
-    } else {                                                                                  \
-      if (inverse)                                                                            \
-        hipLaunchKernelGGL((rqs_fwd_kernel<KM, true, float>), grid, block, 0, stream,          \
-                           (const float*)params, x, y, ldj, B, Dh, K, bound, ldj_init);       \
-      else                                                                                    \
-        hipLaunchKernelGGL((rqs_fwd_kernel<KM, false, float>), grid, block, 0, stream,         \
-                           (const float*)params, x, y, ldj, B, Dh, K, bound, ldj_init);       \
-    }                                                                                         \
-  } while (0)
-  NF_RQS_KMAX(NF_RQS_F);
-#undef NF_RQS_F
-  NF_HIP_CHECK(hipGetLastError());
+  ew_launch<RqsOp>("rqs_fwd", EwFwd{x, y, ldj, ldj_init}, params, params_is_bf16, B, Dh, inverse,
+                   stream, K, bound);
 }
 
 void nf_launch_rqs_bwd(const void* params, int params_is_bf16, const float* x, const float* g_out,
                        const float* g_ldj, void* dparams, float* gx, int B, int Dh, int K,
                        float bound, int inverse, hipStream_t stream) {
-  if (B <= 0 || Dh <= 0) return;
-  if (K < 2 || K > 32 || !(bound > 0.f) || !rqs_row_fits(K, Dh)) {
-    fprintf(stderr, "rqs_bwd: need 2 <= K <= 32, bound > 0 and (3K-1) Dh < 2^29\n");
-    abort();
-  }
-  dim3 grid((B + 3) / 4), block(256);
-#define NF_RQS_B(KM)                                                                          \
-  do {                                                                                        \
-    if (params_is_bf16) {                                                                     \
-      if (inverse)                                                                            \
-        hipLaunchKernelGGL((rqs_bwd_kernel<KM, true, bf16_t>), grid, block, 0, stream,         \
-                           (const bf16_t*)params, x, g_out, g_ldj, (bf16_t*)dparams, gx, B,   \
-                           Dh, K, bound);                                                     \
-      else                                                                                    \
-        hipLaunchKernelGGL((rqs_bwd_kernel<KM, false, bf16_t>), grid, block, 0, stream,        \
-                           (const bf16_t*)params, x, g_out, g_ldj, (bf16_t*)dparams, gx, B,   \
-                           Dh, K, bound);                                                     \
-    } else {                                                                                  \
-      if (inverse)                                                                            \
-        hipLaunchKernelGGL((rqs_bwd_kernel<KM, true, float>), grid, block, 0, stream,          \
-                           (const float*)params, x, g_out, g_ldj, (float*)dparams, gx, B, Dh, \
-                           K, bound);                                                         \
-      else                                                                                    \
-        hipLaunchKernelGGL((rqs_bwd_kernel<KM, false, float>), grid, block, 0, stream,         \
-                           (const float*)params, x, g_out, g_ldj, (float*)dparams, gx, B, Dh, \
-                           K, bound);                                                         \
-    }                                                                                         \
-  } while (0)
-  NF_RQS_KMAX(NF_RQS_B);
-#undef NF_RQS_B
-  NF_HIP_CHECK(hipGetLastError());
+  ew_launch<RqsOp>("rqs_bwd", EwBwd{x, g_out, g_ldj, dparams, gx}, params, params_is_bf16, B, Dh,
+                   inverse, stream, K, bound);
 }
+

@@ -17,7 +17,7 @@ import json
 
 import torch
 
-from .spline_bench import _alternate
+from .timing import alternate
 
 KERNEL_BISECTIONS, KERNEL_NEWTON = 30, 2   # kInvBisect / kInvNewton of csrc/kernels/planar.hip
 
@@ -68,7 +68,7 @@ def main(argv=None):
                 f()
         return run
 
-    us = _alternate({
+    us = alternate({
         "inv": lambda: ops.planar_stack_inv(y, W, Uh, B, a.per_sample, False, out, ldj, saved),
         "inv_step": step(pl.planar_stack_inverse, y),
         "fwd": lambda: ops.planar_stack_fwd(z, W, Uh, B, a.per_sample, False, out, ldj, saved),

@@ -22,7 +22,7 @@ from pathlib import Path
 
 import torch
 
-from .spline_bench import _alternate
+from .timing import alternate
 
 
 def main(argv=None):
@@ -59,7 +59,7 @@ def main(argv=None):
                         8 * D + 12),
             }
             for op, (kern, comp, flops_per_pair) in runs.items():
-                us = _alternate({"kernel": kern, "composite": comp}, a.reps)
+                us = alternate({"kernel": kern, "composite": comp}, a.reps)
                 got, want = kern(), comp()
                 got, want = (got, want) if op == "svgd" else (got[0], want[0])
                 scale = want.abs().max().item()

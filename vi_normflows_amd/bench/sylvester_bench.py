@@ -23,7 +23,7 @@ from pathlib import Path
 
 import torch
 
-from .spline_bench import _alternate
+from .timing import alternate
 
 
 def main(argv=None):
@@ -52,7 +52,7 @@ def main(argv=None):
     # device-to-device copy rate (read + write) on a buffer of the largest parameter block
     src = torch.empty(max(a.rows) * width, device=dev, dtype=torch.float32).normal_(generator=g)
     dst = torch.empty_like(src)
-    copy_us = _alternate({"copy": lambda: dst.copy_(src)}, a.reps)["copy"]
+    copy_us = alternate({"copy": lambda: dst.copy_(src)}, a.reps)["copy"]
     copy_bps = 2 * src.numel() * 4 / (copy_us * 1e-6)
     del src, dst
     flips = [k % 2 for k in range(K)]
@@ -81,7 +81,7 @@ def main(argv=None):
                     return f()
             return run
 
-        us = _alternate({
+        us = alternate({
             "fwd": no_grad(lambda: syl.sylvester_fwd(z, *params, flips)),
             "fwd_composite": no_grad(
                 lambda: syl.sylvester_stack(z, *params, flips, impl="composite")),

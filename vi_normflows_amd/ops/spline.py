@@ -10,52 +10,23 @@ native library is missing. CPU tensors run the torch composite under torch autog
 """
 from __future__ import annotations
 
-import torch
-
+from . import _elementwise as ew
 from . import reference
-from ._ext import native, use_native
+from ._ext import use_native
+
+RQS = ew.Spec("rqs", "rqs_fwd", "rqs_bwd", planes=lambda K: 3 * K - 1, x_side=False)
 
 
 def rqs_fwd(params, x, K: int, bound: float, inverse: bool = False, ldj=None):
     """Raw fused forward on GPU tensors: returns ``(y, ldj)``; a given ``ldj`` [B] is
     accumulated into instead of initialised."""
-    y = torch.empty_like(x)
-    init = ldj is None
-    if init:
-        ldj = torch.empty(x.shape[0], device=x.device, dtype=torch.float32)
-    native().rqs_fwd(params, x, int(K), float(bound), bool(inverse), init, y, ldj)
-    return y, ldj
+    return ew.fwd(RQS, params, x, (int(K), float(bound)), inverse, ldj)
 
 
 def rqs_bwd(params, x, g_out, g_ldj, K: int, bound: float, inverse: bool = False):
     """Raw fused backward on GPU tensors: returns ``(dparams, gx)``; ``x`` is the input of the
     direction taken."""
-    dparams = torch.empty_like(params)
-    gx = torch.empty_like(x)
-    native().rqs_bwd(params, x, g_out, g_ldj, int(K), float(bound), bool(inverse), dparams, gx)
-    return dparams, gx
-
-
-class _RqsFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, params, x, K: int, bound: float, inverse: bool):
-        if params.dtype not in (torch.float32, torch.bfloat16):
-            raise TypeError(f"rqs_transform: GPU params must be fp32 or bf16, got {params.dtype}")
-        pc = params.contiguous()
-        xc = x.to(torch.float32).contiguous()
-        y, ldj = rqs_fwd(pc, xc, K, bound, inverse)
-        ctx.save_for_backward(pc, xc)
-        ctx.K, ctx.bound, ctx.inverse, ctx.x_dtype = K, bound, inverse, x.dtype
-        return y, ldj
-
-    @staticmethod
-    def backward(ctx, gy, gldj):
-        pc, xc = ctx.saved_tensors
-        gy = (gy if gy is not None else torch.zeros_like(xc)).to(torch.float32).contiguous()
-        gl = (gldj if gldj is not None else torch.zeros(xc.shape[0], device=xc.device))
-        gl = gl.to(torch.float32).contiguous()
-        dparams, gx = rqs_bwd(pc, xc, gy, gl, ctx.K, ctx.bound, ctx.inverse)
-        return dparams, gx.to(ctx.x_dtype), None, None, None
+    return ew.bwd(RQS, params, x, g_out, g_ldj, (int(K), float(bound)), inverse)
 
 
 def rqs_transform(params, x, K: int, bound: float, inverse: bool = False):
@@ -64,9 +35,9 @@ def rqs_transform(params, x, K: int, bound: float, inverse: bool = False):
     Returns ``(y, ldj)``: ``y`` [B, Dh] and the per-row log|det| [B] of the direction taken
     (fp32 on the GPU, the dtype of ``x`` on the CPU)."""
     if x.dim() != 2 or params.dim() != 2 or params.shape[0] != x.shape[0] \
-            or params.shape[1] != (3 * K - 1) * x.shape[1]:
+            or params.shape[1] != RQS.planes(K) * x.shape[1]:
         raise ValueError(f"rqs_transform: params {tuple(params.shape)} does not match x "
                          f"{tuple(x.shape)} with K={K} (need [B, (3K-1) Dh])")
     if use_native(params, x):
-        return _RqsFn.apply(params, x, int(K), float(bound), bool(inverse))
+        return ew.ElementwiseFn.apply(params, x, RQS, (int(K), float(bound)), bool(inverse))
     return reference.rqs_transform(params, x, int(K), float(bound), bool(inverse))
