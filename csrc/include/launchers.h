@@ -361,3 +361,34 @@ void nf_launch_vae_step(const NfVaeParams& prm, const float* x, const float* eps
                         int L, float* ws_eact, float* ws_egrad, float* ws_gphi, float* ws_zk,
                         float* ws_dact, float* ws_dgrad, float* ws_dl, float* frow, float* loss,
                         float* zk_out, float* ldj_out, const NfVaeGrads& grd, hipStream_t stream);
+
+// made_sweep.hip: the sequential direction of a MADE-conditioned flow (MAF sampling, IAF
+// inverse) as one degree sweep. W[l] [H, D or H] / b[l] [H] are the L hidden layers, Wo [2D, H] /
+// bo [2D] the output layer (rows i = m, i + D = s), all fp32, unmasked, unit inner stride with row
+// strides in elements; perm [D] and ubeg [L, D + 2] (ubeg[l][t] = number of layer-l units of
+// degree < t) are int32 device arrays; kind 0 = maf_sample (param = bound), 1 = iaf_gated (param =
+// gate_bias), 2 = iaf_affine (param = scale). x [B, D] and ldj [B] are written for every row.
+#define NF_MADE_SWEEP_MAX_HIDDEN 4
+struct NfMadeSweep {
+  const float* W[NF_MADE_SWEEP_MAX_HIDDEN];
+  const float* b[NF_MADE_SWEEP_MAX_HIDDEN];
+  long ldw[NF_MADE_SWEEP_MAX_HIDDEN];
+  const float* Wo;
+  long ldo;
+  const float* bo;
+  const float* v;
+  long ldv;
+  const float* ctx;   // [B, H] added to layer 1's pre-activation, or null
+  long ldc;
+  const int* perm;
+  const int* ubeg;
+  float* x;
+  long ldx;
+  float* ldj;
+  int B, D, H, L, kind;
+  float param;
+};
+// rows per block the launcher picks for (D, H, L): the largest tile whose LDS state fits the
+// budget it requests; 0 = the shape is not supported
+int nf_made_sweep_rows(int D, int H, int L);
+void nf_launch_made_sweep(const NfMadeSweep& s, hipStream_t stream);

@@ -1,0 +1,230 @@
+// Degree sweep: the sequential direction of a MADE-conditioned autoregressive flow (MAF sampling
+// u -> x, IAF inverse y -> z) as ONE masked pass instead of D full MADE passes.
+//
+// made_degrees() gives every hidden layer sorted, non-decreasing degrees, so for the coordinate of
+// degree t (t = 1 .. D, i = perm[t - 1])
+//   * its two outputs m, s read a PREFIX h_L[:c(t)] of the last hidden layer (degrees < t),
+//   * the hidden units of degree t form a contiguous range per layer, and read the first t
+//     coordinates in degree order (layer 1) or a prefix of the layer below (degrees <= t).
+// Walking t upwards is a forward substitution in which every in-mask weight is used exactly once
+// per row; entries outside the masks are never read, so the weights need not be pre-masked.
+//
+// Mapping: a block of 256 threads owns a tile of R rows and keeps their state in LDS in fp32: x in
+// DEGREE order (xs[r][t - 1], staged from v and overwritten coordinate by coordinate) and every
+// hidden layer (hs[l][r][k], pre-filled with bias (+ context projection), overwritten by the
+// activation). Each weight is read from global memory once per block and used for all R rows.
+//   outputs of step t: the four waves take the 64-wide chunks of [0, c) round-robin, each lane
+//     accumulating m and s of all R rows; a wave butterfly, then thread r adds the four wave
+//     partials in wave order and applies the transform of coordinate i;
+//   hidden units of degree t: one wave per unit, lanes strided over the inputs, wave butterfly.
+// A row's sums therefore depend only on (c, t, lane, wave), never on R, on the row's place in the
+// tile or on the batch size: a row's result is bitwise the same in any batch. No atomics.
+// All arithmetic is fp32 with explicit fmaf; tanhf / expf / log1pf are the accurate library forms
+// (errors feed forward through up to D dependent steps).
+#include "nf_common.h"
+
+namespace {
+
+constexpr int NT = 256;          // threads per block (4 waves)
+constexpr int NW = NT / 64;
+constexpr int kLdsBudget = 81920;  // bytes per block: two blocks stay resident on a 160 KiB CU
+// Rows per block: the largest power of two <= kMaxRows whose state fits kLdsBudget. A step is a
+// chain of dependent waits (weights, LDS, shuffles, three barriers) that one block cannot fill, so
+// blocks sharing a CU matter more than weight reuse: at (B, D, H) = (4096, 256, 512) a launch took
+// 2.24 / 1.35 / 1.03 / 1.27 ms with 16 / 8 / 4 / 2 rows (docs/PERF_NOTES.md, "Degree sweep").
+constexpr int kMaxRows = 8;
+
+struct SweepArgs {
+  const float* W[NF_MADE_SWEEP_MAX_HIDDEN];
+  const float* b[NF_MADE_SWEEP_MAX_HIDDEN];
+  long ldw[NF_MADE_SWEEP_MAX_HIDDEN];
+  const float* Wo; long ldo;
+  const float* bo;
+  const float* v; long ldv;
+  const float* ctx; long ldc;     // [B, H] added to layer 1's pre-activation, or null
+  const int* perm;                // [D]: coordinate of degree t is perm[t - 1]
+  const int* ubeg;                // [L, D + 2]: ubeg[l][t] = #{k : deg_l[k] < t}
+  float* x; long ldx;
+  float* ldj;
+  int B, D, H, L, kind;
+  float p;                        // bound (maf_sample) | gate_bias (iaf_gated) | scale (iaf_affine)
+};
+
+__host__ __device__ inline long sweep_lds_floats(int R, int D, int H, int L) {
+  return (long)R * ((long)D + (long)L * H) + D + NW * 2 * R;
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// one coordinate: value v, conditioner outputs m, s -> x; returns the log-det share
+__device__ __forceinline__ float sweep_transform(int kind, float p, float v, float m, float s,
+                                                 float& x) {
+  if (kind == 0) {             // MAF sampling: x = v exp(a) + m, a = p tanh(s / p)
+    const float a = p * tanhf(s / p);
+    x = fmaf(v, expf(a), m);
+    return a;
+  }
+  if (kind == 1) {             // gated IAF inverse: v = g x + (1 - g) m, g = sigmoid(s + p)
+    const float z = s + p;
+    const float e = expf(-fabsf(z));
+    const float g = z >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+    x = (v - (1.f - g) * m) / g;
+    return log1pf(e) - fminf(z, 0.f);   // -logsigmoid(z)
+  }
+  const float c = p * tanhf(s);   // affine IAF inverse: v = x exp(c) + m
+  x = (v - m) * expf(-c);
+  return -c;
+}
+
+template <int R>
+__global__ __launch_bounds__(NT) void made_sweep_kernel(const SweepArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int D = a.D, H = a.H, L = a.L;
+  float* xs = lds;                          // [R][D], degree order
+  float* hs = xs + (long)R * D;             // [L][R][H]
+  float* part = hs + (long)L * R * H;       // [NW][2][R] wave partials of (m, s)
+  int* pl = reinterpret_cast<int*>(part + NW * 2 * R);   // [D] perm
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const long row0 = (long)blockIdx.x * R;
+  const int W2 = D + 2;
+
+  for (int p = tid; p < D; p += NT) pl[p] = clampi(a.perm[p], 0, D - 1);
+  __syncthreads();
+  // stage v in degree order; rows past the batch run on zeros and are never stored
+  for (int r = 0; r < R; ++r) {
+    const long row = row0 + r;
+    for (int p = tid; p < D; p += NT)
+      xs[r * D + p] = row < a.B ? a.v[row * a.ldv + pl[p]] : 0.f;
+    for (int l = 0; l < L; ++l)
+      for (int k = tid; k < H; k += NT) {
+        float bv = a.b[l][k];
+        if (l == 0 && a.ctx != nullptr && row < a.B) bv += a.ctx[row * a.ldc + k];
+        hs[((long)l * R + r) * H + k] = bv;
+      }
+  }
+  __syncthreads();
+
+  const float* hL = hs + (long)(L - 1) * R * H;
+  float ldj = 0.f;
+  for (int t = 1; t <= D; ++t) {
+    const int i = pl[t - 1];
+    const float bm = a.bo[i], bs = a.bo[i + D];
+    // ---- outputs m, s of coordinate i over h_L[:c]
+    {
+      const int c = clampi(a.ubeg[(L - 1) * W2 + t], 0, H);
+      const float* wm = a.Wo + (long)i * a.ldo;
+      const float* ws = a.Wo + (long)(i + D) * a.ldo;
+      float am[R], as[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) am[r] = as[r] = 0.f;
+#pragma unroll 2
+      for (int k = wid * 64 + lane; k < c; k += NT) {
+        const float wmk = wm[k], wsk = ws[k];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const float hv = hL[r * H + k];
+          am[r] = fmaf(wmk, hv, am[r]);
+          as[r] = fmaf(wsk, hv, as[r]);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const float sm = nf::wave_sum(am[r]), ss = nf::wave_sum(as[r]);
+        if (lane == r) {
+          part[(wid * 2 + 0) * R + r] = sm;
+          part[(wid * 2 + 1) * R + r] = ss;
+        }
+      }
+    }
+    __syncthreads();
+    if (tid < R) {
+      float m = part[tid], s = part[R + tid];
+#pragma unroll
+      for (int w = 1; w < NW; ++w) {
+        m += part[(w * 2 + 0) * R + tid];
+        s += part[(w * 2 + 1) * R + tid];
+      }
+      float xi;
+      ldj += sweep_transform(a.kind, a.p, xs[tid * D + t - 1], bm + m, bs + s, xi);
+      xs[tid * D + t - 1] = xi;
+    }
+    __syncthreads();
+    // ---- hidden units of degree t, layer by layer
+    for (int l = 0; l < L; ++l) {
+      const int u0 = clampi(a.ubeg[l * W2 + t], 0, H);
+      const int u1 = clampi(a.ubeg[l * W2 + t + 1], u0, H);
+      if (u1 == u0) continue;   // block-uniform
+      const int n = l == 0 ? t : clampi(a.ubeg[(l - 1) * W2 + t + 1], 0, H);
+      const float* in = l == 0 ? xs : hs + (long)(l - 1) * R * H;
+      const int ldi = l == 0 ? D : H;
+      float* out = hs + (long)l * R * H;
+      for (int k = u0 + wid; k < u1; k += NW) {
+        const float* w = a.W[l] + (long)k * a.ldw[l];
+        float acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = 0.f;
+#pragma unroll 2
+        for (int j = lane; j < n; j += 64) {
+          const float wv = l == 0 ? w[pl[j]] : w[j];
+#pragma unroll
+          for (int r = 0; r < R; ++r) acc[r] = fmaf(wv, in[r * ldi + j], acc[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const float sum = nf::wave_sum(acc[r]);
+          if (lane == r) out[r * H + k] = fmaxf(out[r * H + k] + sum, 0.f);
+        }
+      }
+      __syncthreads();
+    }
+  }
+
+  if (tid < R && row0 + tid < a.B) a.ldj[row0 + tid] = ldj;
+  for (int r = 0; r < R; ++r) {
+    const long row = row0 + r;
+    if (row >= a.B) break;
+    for (int p = tid; p < D; p += NT) a.x[row * a.ldx + pl[p]] = xs[r * D + p];
+  }
+}
+
+template <int R>
+void launch(const SweepArgs& a, hipStream_t stream) {
+  const size_t bytes = sizeof(float) * sweep_lds_floats(R, a.D, a.H, a.L);
+  static bool attr_set = false;
+  if (!attr_set) {
+    NF_HIP_CHECK(hipFuncSetAttribute((const void*)made_sweep_kernel<R>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget));
+    attr_set = true;
+  }
+  const long blocks = ((long)a.B + R - 1) / R;
+  hipLaunchKernelGGL(made_sweep_kernel<R>, dim3((unsigned)blocks), dim3(NT), bytes, stream, a);
+  NF_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace
+
+int nf_made_sweep_rows(int D, int H, int L) {
+  if (D < 1 || H < 1 || L < 1 || L > NF_MADE_SWEEP_MAX_HIDDEN) return 0;
+  for (int R = kMaxRows; R >= 1; R >>= 1)
+    if (sizeof(float) * sweep_lds_floats(R, D, H, L) <= (size_t)kLdsBudget) return R;
+  return 0;
+}
+
+void nf_launch_made_sweep(const NfMadeSweep& s, hipStream_t stream) {
+  SweepArgs a{};
+  for (int l = 0; l < s.L; ++l) { a.W[l] = s.W[l]; a.b[l] = s.b[l]; a.ldw[l] = s.ldw[l]; }
+  a.Wo = s.Wo; a.ldo = s.ldo; a.bo = s.bo;
+  a.v = s.v; a.ldv = s.ldv; a.ctx = s.ctx; a.ldc = s.ldc;
+  a.perm = s.perm; a.ubeg = s.ubeg;
+  a.x = s.x; a.ldx = s.ldx; a.ldj = s.ldj;
+  a.B = s.B; a.D = s.D; a.H = s.H; a.L = s.L; a.kind = s.kind; a.p = s.param;
+  switch (nf_made_sweep_rows(s.D, s.H, s.L)) {
+    case 8: launch<8>(a, stream); break;
+    case 4: launch<4>(a, stream); break;
+    case 2: launch<2>(a, stream); break;
+    case 1: launch<1>(a, stream); break;
+    default:
+      nf_throw_hip_error(hipErrorInvalidValue, "made_sweep: shape exceeds the LDS budget",
+                         __FILE__, __LINE__);
+  }
+}

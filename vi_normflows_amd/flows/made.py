@@ -12,7 +12,13 @@ prefix/suffix of the reduction dimension per output tile, which the masked MFMA 
   log|det| = sum log sigma.  ``mode="affine"``: z' = z exp(tanh-bounded s) + m.
 * MAF (Papamakarios et al. 2017), density direction in one pass:
   [mu, alpha] = MADE(x);  u = (x - mu) exp(-alpha);  log|det du/dx| = -sum alpha.
-  Sampling inverts sequentially (D MADE passes).
+
+The other direction of each (MAF sampling u -> x, IAF inverse y -> z) is sequential in the
+coordinates. Because the hidden degrees are sorted it is still one masked pass, a forward
+substitution in degree order: ``ops.autoregressive`` (``csrc/kernels/made_sweep.hip``) runs it for
+fp32 GPU tensors when nothing needs a graph. Otherwise - CPU tensors, grad mode on with an input
+or parameter that requires grad, a non-ReLU MADE, a shape outside the kernel's LDS budget - it is
+a loop of D full MADE passes.
 """
 from __future__ import annotations
 
@@ -148,7 +154,12 @@ class IAF(Flow):
         return y, ldj
 
     def inverse(self, y, context=None):
-        """Sequential inverse (D passes)."""
+        """Inverse y -> z, ``(z, -log|det dy/dz|)``. On the GPU, when nothing needs a graph, one
+        degree sweep (``ops.autoregressive``); else sequential: D MADE passes, differentiable."""
+        from ..ops import autoregressive
+
+        if autoregressive.dispatch(self, y, context):
+            return autoregressive.made_sweep_flow(self, y, context)
         z = torch.zeros_like(y)
         for i in self._order_idx():
             out = self.made(z, context)
@@ -191,7 +202,13 @@ class MAF(Flow):
         return (x - mu) * torch.exp(-alpha), -alpha.sum(1)
 
     def forward(self, u, context=None):
-        """Sampling direction u -> x: D sequential MADE passes."""
+        """Sampling direction u -> x, ``(x, log|det dx/du|)``. On the GPU, when nothing needs a
+        graph (grad mode off, or neither the input nor a parameter requires grad), one degree
+        sweep (``ops.autoregressive``); else D sequential MADE passes, differentiable."""
+        from ..ops import autoregressive
+
+        if autoregressive.dispatch(self, u, context):
+            return autoregressive.made_sweep_flow(self, u, context)
         x = torch.zeros_like(u)
         for i in torch.argsort(self.made.order).tolist():
             mu, alpha = self._mu_alpha(x, context)

@@ -98,7 +98,9 @@ class DSFAutoregressive(Flow):
     def inverse(self, y, context=None):
         """Sequential inverse (D MADE passes, each followed by the root solve of one
         coordinate); returns ``(z, -ldj)`` with ldj from one forward pass at z. For sampling
-        and checks: it runs without a graph and is not differentiated."""
+        and checks: it runs without a graph and is not differentiated. The degree sweep of
+        ``ops.autoregressive`` (one masked pass for MAF / IAF) would apply here too, with the
+        root solve as the per-coordinate transform; this layer has not adopted it yet."""
         z = torch.zeros_like(y)
         for i in torch.argsort(self.made.order).tolist():
             p_i = self.made(z, context)[:, :, i].contiguous()          # [N, 3 units]

@@ -50,7 +50,10 @@ class MAFDensity(nn.Module):
 
     @torch.no_grad()
     def sample(self, n: int, generator=None):
-        """Sequential inversion (D MADE passes per layer) - slow by construction."""
+        """Samples x = f_1 o ... o f_L(u), u ~ N(0, I). On the GPU each layer is one degree sweep
+        over the layer's fp32 parameters (``ops.autoregressive``, one masked pass); on the CPU,
+        or for a shape outside the kernel's LDS budget, each layer inverts sequentially (D MADE
+        passes)."""
         u = torch.randn(n, self.cfg.dim, generator=generator,
                         device=next(self.parameters()).device)
         for f in reversed(self.layers):

@@ -461,6 +461,28 @@ class MAFEngine(FlatEngine):
             return None, self.Xbf[l + 1]
         return self.X[l + 1], (None if self._lean8() else self.Xbf[l + 1])
 
+    # ------------------------------------------------------------------ sampling
+    @torch.no_grad()
+    def sample(self, n: int, generator=None) -> torch.Tensor:
+        """``n`` samples x [n, D] (fp32) of the trained density: u = ``torch.randn(n, D,
+        generator=generator)`` drawn on the generator's device (the engine's without one), pushed
+        through the layers L-1 .. 0 in the sampling direction. Each layer is one degree sweep
+        (``ops.autoregressive.made_sweep``: the HIP kernel on the GPU, the torch composite on the
+        CPU) over views of the fp32 master weights, which the sweep does not need masked. Reads
+        parameters only: no training state changes."""
+        from ..ops.autoregressive import made_sweep
+
+        cfg, P = self.cfg, self.params
+        dev = generator.device if generator is not None else self.device
+        x = torch.randn(int(n), cfg.dim, generator=generator, device=dev,
+                        dtype=torch.float32).to(self.device)
+        orders = (None, torch.arange(cfg.dim, 0, -1))
+        for l in range(cfg.n_layers - 1, -1, -1):
+            x, _ = made_sweep(x, [P.p(f"l{l}.W1"), P.p(f"l{l}.W2")],
+                              [P.p(f"l{l}.b1"), P.p(f"l{l}.b2")], orders[l % 2], "maf_sample",
+                              bound=cfg.alpha_bound)
+        return x
+
     def s_raw(self, l: int) -> torch.Tensor:
         """s_raw of layer l (the fused engine keeps only this half of [mu | s_raw])."""
         return self.S[l] if self.fuse else self.O[l][:, self.cfg.dim:]

@@ -5,7 +5,8 @@
 
 Tasks: flow_vi (non-amortized VI on a named target), realnvp_vi (explicit-backward engine,
 data parallel, hipGraph), planar_vae (reference MNIST workload on synthetic binary data or a
-user .npy), iaf_vae, maf_density, bbvi. Writes ``<out_dir>/<name>/``: config.json,
+user .npy), iaf_vae, maf_density (``extra.sample_n=N`` also writes N samples of the trained
+density to ``samples.npy``), bbvi. Writes ``<out_dir>/<name>/``: config.json,
 metrics.jsonl, final.json, checkpoints, figures and (planar_vae) the reference ``.npy``
 weights + ``free_energy.txt`` line.
 """
@@ -310,10 +311,23 @@ def run_iaf_vae(cfg, out, info, logger):
     return {"free_energy": tr.history[-1]["F"], "engine": "module"}
 
 
+def _save_maf_samples(cfg, out, info, sampler) -> None:
+    """``extra.sample_n`` = N > 0: N samples of the trained density as ``samples.npy`` [N, dim]
+    (main rank; generator seeded from the run's seed)."""
+    n = int(cfg.extra.get("sample_n", 0))
+    if n <= 0 or not info.is_main:
+        return
+    import numpy as np
+
+    g = torch.Generator().manual_seed(rank_seed(cfg.seed, info.rank) + 1)
+    np.save(out / "samples.npy", sampler(n, g).detach().float().cpu().numpy())
+
+
 @_closes_runners
 def run_maf(cfg, out, info, logger):
     """MAF density estimation. ``extra.impl``: "engine" (default: flat-buffer explicit-backward
-    engine, fp8/bf16 forward, DP runner + hipGraph) or "module" (autograd MAFDensity)."""
+    engine, fp8/bf16 forward, DP runner + hipGraph) or "module" (autograd MAFDensity).
+    ``extra.sample_n`` = N writes N samples of the trained density to ``samples.npy``."""
     dev = _device(cfg, info)
     if cfg.extra.get("impl", "engine") == "engine":
         from .models.maf_engine import MAFEngine, MAFEngineConfig
@@ -325,6 +339,7 @@ def run_maf(cfg, out, info, logger):
         _engine_loop(cfg, out, info, logger, eng, lambda sps: {
             "nll": float(eng.loss.item()), "grad_norm": eng.log_record()["grad_norm"],
             "samples_per_s": sps, **eng.fp8_saturation()})
+        _save_maf_samples(cfg, out, info, eng.sample)
         return {"nll": float(eng.loss.item()), "nll_floor_entropy": mc.entropy(),
                 "precision": mc.precision if dev.type == "cuda" else "fp32"}
 
@@ -346,6 +361,8 @@ def run_maf(cfg, out, info, logger):
                  TrainConfig(iters=cfg.iters, lr=cfg.lr, optimizer=cfg.optimizer,
                              log_every=cfg.log_every), logger=logger)
     tr.fit()
+    _save_maf_samples(cfg, out, info, lambda n, g: model.sample(
+        n, generator=torch.Generator(device=dev).manual_seed(g.initial_seed())))
     return {"nll": tr.history[-1]["F"], "nll_floor_entropy": banana_entropy(cfg.dim)}
 
 
