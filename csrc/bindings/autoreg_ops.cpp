@@ -1,5 +1,6 @@
-// TORCH_LIBRARY fragment for the autoregressive degree sweep (made_sweep.hip): MAF sampling and
-// the IAF inverse in one masked pass. Not differentiable.
+// TORCH_LIBRARY fragment for the autoregressive degree sweeps: MAF sampling and the IAF inverse
+// (made_sweep.hip) and the inverse of a MADE-conditioned DSF layer (dsf_sweep.hip) in one masked
+// pass. Not differentiable.
 #include <torch/library.h>
 #include <ATen/ATen.h>
 
@@ -9,73 +10,100 @@
 namespace {
 
 // fp32 GPU [rows, cols] with unit inner stride; returns the row stride in elements
-long mat_stride(const at::Tensor& t, const char* n, int64_t rows, int64_t cols,
+long mat_stride(const char* op, const at::Tensor& t, const char* n, int64_t rows, int64_t cols,
                 const at::Device& dev) {
-  TORCH_CHECK(t.is_cuda() && t.device() == dev, "made_sweep: ", n, " must be on the device of v");
-  TORCH_CHECK(t.scalar_type() == at::kFloat, "made_sweep: ", n, " must be fp32, got ",
+  TORCH_CHECK(t.is_cuda() && t.device() == dev, op, ": ", n, " must be on the device of v");
+  TORCH_CHECK(t.scalar_type() == at::kFloat, op, ": ", n, " must be fp32, got ",
               t.scalar_type());
-  TORCH_CHECK(t.dim() == 2 && t.size(0) == rows && t.size(1) == cols, "made_sweep: ", n,
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == rows && t.size(1) == cols, op, ": ", n,
               " has shape ", t.sizes(), ", expected [", rows, ", ", cols, "]");
-  TORCH_CHECK(cols == 1 || t.stride(1) == 1, "made_sweep: ", n, " must have unit inner stride");
+  TORCH_CHECK(cols == 1 || t.stride(1) == 1, op, ": ", n, " must have unit inner stride");
   const int64_t rs = rows > 1 ? t.stride(0) : cols;
-  TORCH_CHECK(rs >= cols, "made_sweep: ", n, " has overlapping rows (row stride ", rs, ")");
+  TORCH_CHECK(rs >= cols, op, ": ", n, " has overlapping rows (row stride ", rs, ")");
   return (long)rs;
 }
 
-void chk_vec(const at::Tensor& t, const char* n, int64_t numel, at::ScalarType st,
+void chk_vec(const char* op, const at::Tensor& t, const char* n, int64_t numel, at::ScalarType st,
              const at::Device& dev) {
   TORCH_CHECK(t.is_cuda() && t.device() == dev && t.scalar_type() == st && t.is_contiguous() &&
                   t.numel() == numel,
-              "made_sweep: ", n, " must be a contiguous ", st, " tensor of ", numel,
+              op, ": ", n, " must be a contiguous ", st, " tensor of ", numel,
               " elements on the device of v");
+}
+
+// The checks and the launch struct both sweeps share; the output layer has out_mult rows per
+// coordinate. The LDS-budget check is the caller's (it depends on the kernel).
+NfMadeSweep sweep_args(const char* op, const at::Tensor& v, at::TensorList weights,
+                       at::TensorList biases, const at::Tensor& perm, const at::Tensor& ubeg,
+                       int64_t out_mult, const c10::optional<at::Tensor>& ctx_bias,
+                       const at::Tensor& x, const at::Tensor& ldj) {
+  TORCH_CHECK(v.is_cuda() && v.dim() == 2, op, ": v must be a GPU tensor [B, D]");
+  const int64_t L = (int64_t)weights.size() - 1;
+  TORCH_CHECK(L >= 1 && L <= NF_MADE_SWEEP_MAX_HIDDEN && biases.size() == weights.size(),
+              op, ": need 1 .. ", NF_MADE_SWEEP_MAX_HIDDEN,
+              " hidden layers plus the output layer, one bias per weight");
+  TORCH_CHECK(weights[0].dim() == 2, op, ": a hidden weight must be a matrix");
+  const int64_t B = v.size(0), D = v.size(1), H = weights[0].size(0);
+  TORCH_CHECK(B >= 1 && B < (int64_t(1) << 31) && D >= 1 && H >= 1 && D < (1 << 24) &&
+                  H < (1 << 24),
+              op, ": bad sizes B = ", B, ", D = ", D, ", H = ", H);
+  const auto dev = v.device();
+  NfMadeSweep s{};
+  s.B = (int)B; s.D = (int)D; s.H = (int)H; s.L = (int)L;
+  s.ldv = mat_stride(op, v, "v", B, D, dev);
+  s.v = v.data_ptr<float>();
+  for (int64_t l = 0; l < L; ++l) {
+    s.ldw[l] = mat_stride(op, weights[l], "a hidden weight", H, l == 0 ? D : H, dev);
+    s.W[l] = weights[l].data_ptr<float>();
+    chk_vec(op, biases[l], "a hidden bias", H, at::kFloat, dev);
+    s.b[l] = biases[l].data_ptr<float>();
+  }
+  s.ldo = mat_stride(op, weights[L], "the output weight", out_mult * D, H, dev);
+  s.Wo = weights[L].data_ptr<float>();
+  chk_vec(op, biases[L], "the output bias", out_mult * D, at::kFloat, dev);
+  s.bo = biases[L].data_ptr<float>();
+  chk_vec(op, perm, "perm", D, at::kInt, dev);
+  chk_vec(op, ubeg, "ubeg", L * (D + 2), at::kInt, dev);
+  s.perm = perm.data_ptr<int>();
+  s.ubeg = ubeg.data_ptr<int>();
+  if (ctx_bias.has_value() && ctx_bias->defined()) {
+    s.ldc = mat_stride(op, *ctx_bias, "ctx_bias", B, H, dev);
+    s.ctx = ctx_bias->data_ptr<float>();
+  }
+  s.ldx = mat_stride(op, x, "x", B, D, dev);
+  s.x = x.data_ptr<float>();
+  chk_vec(op, ldj, "ldj", B, at::kFloat, dev);
+  s.ldj = ldj.data_ptr<float>();
+  return s;
 }
 
 void made_sweep(const at::Tensor& v, at::TensorList weights, at::TensorList biases,
                 const at::Tensor& perm, const at::Tensor& ubeg, int64_t kind, double param,
                 const c10::optional<at::Tensor>& ctx_bias, const at::Tensor& x,
                 const at::Tensor& ldj) {
-  TORCH_CHECK(v.is_cuda() && v.dim() == 2, "made_sweep: v must be a GPU tensor [B, D]");
   TORCH_CHECK(kind >= 0 && kind <= 2,
               "made_sweep: unknown kind ", kind, " (0 maf_sample, 1 iaf_gated, 2 iaf_affine)");
-  const int64_t L = (int64_t)weights.size() - 1;
-  TORCH_CHECK(L >= 1 && L <= NF_MADE_SWEEP_MAX_HIDDEN && biases.size() == weights.size(),
-              "made_sweep: need 1 .. ", NF_MADE_SWEEP_MAX_HIDDEN,
-              " hidden layers plus the output layer, one bias per weight");
-  const int64_t B = v.size(0), D = v.size(1), H = weights[0].size(0);
-  TORCH_CHECK(B >= 1 && B < (int64_t(1) << 31) && D >= 1 && H >= 1 && D < (1 << 24) &&
-                  H < (1 << 24),
-              "made_sweep: bad sizes B = ", B, ", D = ", D, ", H = ", H);
-  TORCH_CHECK(nf_made_sweep_rows((int)D, (int)H, (int)L) > 0, "made_sweep: (D, H, L) = (", D, ", ",
-              H, ", ", L, ") exceeds the kernel's LDS budget (made_sweep_supported)");
-  const auto dev = v.device();
-  NfMadeSweep s{};
-  s.B = (int)B; s.D = (int)D; s.H = (int)H; s.L = (int)L; s.kind = (int)kind;
+  NfMadeSweep s = sweep_args("made_sweep", v, weights, biases, perm, ubeg, 2, ctx_bias, x, ldj);
+  TORCH_CHECK(nf_made_sweep_rows(s.D, s.H, s.L) > 0, "made_sweep: (D, H, L) = (", s.D, ", ", s.H,
+              ", ", s.L, ") exceeds the kernel's LDS budget (made_sweep_supported)");
+  s.kind = (int)kind;
   s.param = (float)param;
-  s.ldv = mat_stride(v, "v", B, D, dev);
-  s.v = v.data_ptr<float>();
-  for (int64_t l = 0; l < L; ++l) {
-    s.ldw[l] = mat_stride(weights[l], "a hidden weight", H, l == 0 ? D : H, dev);
-    s.W[l] = weights[l].data_ptr<float>();
-    chk_vec(biases[l], "a hidden bias", H, at::kFloat, dev);
-    s.b[l] = biases[l].data_ptr<float>();
-  }
-  s.ldo = mat_stride(weights[L], "the output weight", 2 * D, H, dev);
-  s.Wo = weights[L].data_ptr<float>();
-  chk_vec(biases[L], "the output bias", 2 * D, at::kFloat, dev);
-  s.bo = biases[L].data_ptr<float>();
-  chk_vec(perm, "perm", D, at::kInt, dev);
-  chk_vec(ubeg, "ubeg", L * (D + 2), at::kInt, dev);
-  s.perm = perm.data_ptr<int>();
-  s.ubeg = ubeg.data_ptr<int>();
-  if (ctx_bias.has_value() && ctx_bias->defined()) {
-    s.ldc = mat_stride(*ctx_bias, "ctx_bias", B, H, dev);
-    s.ctx = ctx_bias->data_ptr<float>();
-  }
-  s.ldx = mat_stride(x, "x", B, D, dev);
-  s.x = x.data_ptr<float>();
-  chk_vec(ldj, "ldj", B, at::kFloat, dev);
-  s.ldj = ldj.data_ptr<float>();
   nf_launch_made_sweep(s, cur_stream());
+}
+
+// y [B, D] -> z = x, ldj of the inverse of a DSF layer with `units` sigmoid units per coordinate;
+// the output layer is [3 units D, H] plane-major (MADE(out_mult = 3 units)).
+void dsf_sweep(const at::Tensor& y, at::TensorList weights, at::TensorList biases,
+               const at::Tensor& perm, const at::Tensor& ubeg, int64_t units,
+               const c10::optional<at::Tensor>& ctx_bias, const at::Tensor& x,
+               const at::Tensor& ldj) {
+  TORCH_CHECK(units >= 1 && units <= 32, "dsf_sweep: need 1 <= units <= 32, got ", units);
+  NfMadeSweep s =
+      sweep_args("dsf_sweep", y, weights, biases, perm, ubeg, 3 * units, ctx_bias, x, ldj);
+  TORCH_CHECK(nf_dsf_sweep_rows(s.D, s.H, s.L, (int)units) > 0, "dsf_sweep: (D, H, L, U) = (", s.D,
+              ", ", s.H, ", ", s.L, ", ", units,
+              ") exceeds the kernel's LDS budget (dsf_sweep_supported)");
+  nf_launch_dsf_sweep(s, (int)units, cur_stream());
 }
 
 // rows per block for (D, H, L); 0 when the shape does not fit
@@ -87,6 +115,18 @@ int64_t made_sweep_rows(int64_t D, int64_t H, int64_t L) {
 
 bool made_sweep_supported(int64_t D, int64_t H, int64_t L) { return made_sweep_rows(D, H, L) > 0; }
 
+// rows per block for (D, H, L, U); 0 when the shape does not fit or U is out of range
+int64_t dsf_sweep_rows(int64_t D, int64_t H, int64_t L, int64_t U) {
+  if (D < 1 || H < 1 || L < 1 || D >= (1 << 24) || H >= (1 << 24) ||
+      L > NF_MADE_SWEEP_MAX_HIDDEN || U < 1 || U > 32)
+    return 0;
+  return nf_dsf_sweep_rows((int)D, (int)H, (int)L, (int)U);
+}
+
+bool dsf_sweep_supported(int64_t D, int64_t H, int64_t L, int64_t U) {
+  return dsf_sweep_rows(D, H, L, U) > 0;
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(vinf, m) {
@@ -94,8 +134,13 @@ TORCH_LIBRARY_FRAGMENT(vinf, m) {
         "int kind, float param, Tensor? ctx_bias, Tensor(a!) x, Tensor(b!) ldj) -> ()");
   m.def("made_sweep_rows(int D, int H, int L) -> int", &made_sweep_rows);
   m.def("made_sweep_supported(int D, int H, int L) -> bool", &made_sweep_supported);
+  m.def("dsf_sweep(Tensor y, Tensor[] weights, Tensor[] biases, Tensor perm, Tensor ubeg, "
+        "int units, Tensor? ctx_bias, Tensor(a!) x, Tensor(b!) ldj) -> ()");
+  m.def("dsf_sweep_rows(int D, int H, int L, int U) -> int", &dsf_sweep_rows);
+  m.def("dsf_sweep_supported(int D, int H, int L, int U) -> bool", &dsf_sweep_supported);
 }
 
 TORCH_LIBRARY_IMPL(vinf, CUDA, m) {
   m.impl("made_sweep", &made_sweep);
+  m.impl("dsf_sweep", &dsf_sweep);
 }

@@ -29,8 +29,10 @@
 #include <stdlib.h>
 
 // The element math is __host__ __device__ so it can also be exercised by a host program; the
-// fast intrinsics exist on the device only.
-#if defined(__HIP_DEVICE_COMPILE__)
+// fast intrinsics exist on the device only. A unit that defines EW_ACCURATE_MATH before its first
+// include gets the accurate library forms on the device too (dsf_sweep.hip, for its accuracy
+// comparison).
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(EW_ACCURATE_MATH)
 #define EW_EXP(v) __expf(v)
 #define EW_LOG(v) __logf(v)
 #define EW_RCP(v) __builtin_amdgcn_rcpf(v)

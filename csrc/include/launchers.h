@@ -392,3 +392,12 @@ struct NfMadeSweep {
 // budget it requests; 0 = the shape is not supported
 int nf_made_sweep_rows(int D, int H, int L);
 void nf_launch_made_sweep(const NfMadeSweep& s, hipStream_t stream);
+
+// dsf_sweep.hip: the inverse of a MADE-conditioned deep sigmoidal flow layer (y -> z) as one
+// degree sweep. The tensors are those of NfMadeSweep (v = y, x = z; kind and param unused) except
+// the output layer: Wo [3U D, H] / bo [3U D] plane-major (row k D + i is plane k of coordinate i;
+// planes [0, U) raw slopes, [U, 2U) shifts, [2U, 3U) mixture logits), 1 <= U <= 32. ldj [B] is
+// minus sum_i log dy_i/dz_i at the recovered z.
+// rows per block for (D, H, L, U); 0 = the shape is not supported
+int nf_dsf_sweep_rows(int D, int H, int L, int U);
+void nf_launch_dsf_sweep(const NfMadeSweep& s, int U, hipStream_t stream);

@@ -21,40 +21,17 @@
 // tile or on the batch size: a row's result is bitwise the same in any batch. No atomics.
 // All arithmetic is fp32 with explicit fmaf; tanhf / expf / log1pf are the accurate library forms
 // (errors feed forward through up to D dependent steps).
-#include "nf_common.h"
+// The arguments are those of made_sweep_common.h, the staging, the hidden-unit phase and the final
+// store the body fragments of made_sweep_phases.h (both also used by dsf_sweep.hip).
+#include "made_sweep_common.h"
 
 namespace {
 
-constexpr int NT = 256;          // threads per block (4 waves)
-constexpr int NW = NT / 64;
-constexpr int kLdsBudget = 81920;  // bytes per block: two blocks stay resident on a 160 KiB CU
-// Rows per block: the largest power of two <= kMaxRows whose state fits kLdsBudget. A step is a
-// chain of dependent waits (weights, LDS, shuffles, three barriers) that one block cannot fill, so
-// blocks sharing a CU matter more than weight reuse: at (B, D, H) = (4096, 256, 512) a launch took
-// 2.24 / 1.35 / 1.03 / 1.27 ms with 16 / 8 / 4 / 2 rows (docs/PERF_NOTES.md, "Degree sweep").
-constexpr int kMaxRows = 8;
-
-struct SweepArgs {
-  const float* W[NF_MADE_SWEEP_MAX_HIDDEN];
-  const float* b[NF_MADE_SWEEP_MAX_HIDDEN];
-  long ldw[NF_MADE_SWEEP_MAX_HIDDEN];
-  const float* Wo; long ldo;
-  const float* bo;
-  const float* v; long ldv;
-  const float* ctx; long ldc;     // [B, H] added to layer 1's pre-activation, or null
-  const int* perm;                // [D]: coordinate of degree t is perm[t - 1]
-  const int* ubeg;                // [L, D + 2]: ubeg[l][t] = #{k : deg_l[k] < t}
-  float* x; long ldx;
-  float* ldj;
-  int B, D, H, L, kind;
-  float p;                        // bound (maf_sample) | gate_bias (iaf_gated) | scale (iaf_affine)
-};
+using namespace nf_sweep;
 
 __host__ __device__ inline long sweep_lds_floats(int R, int D, int H, int L) {
   return (long)R * ((long)D + (long)L * H) + D + NW * 2 * R;
 }
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // one coordinate: value v, conditioner outputs m, s -> x; returns the log-det share
 __device__ __forceinline__ float sweep_transform(int kind, float p, float v, float m, float s,
@@ -88,21 +65,8 @@ __global__ __launch_bounds__(NT) void made_sweep_kernel(const SweepArgs a) {
   const long row0 = (long)blockIdx.x * R;
   const int W2 = D + 2;
 
-  for (int p = tid; p < D; p += NT) pl[p] = clampi(a.perm[p], 0, D - 1);
-  __syncthreads();
-  // stage v in degree order; rows past the batch run on zeros and are never stored
-  for (int r = 0; r < R; ++r) {
-    const long row = row0 + r;
-    for (int p = tid; p < D; p += NT)
-      xs[r * D + p] = row < a.B ? a.v[row * a.ldv + pl[p]] : 0.f;
-    for (int l = 0; l < L; ++l)
-      for (int k = tid; k < H; k += NT) {
-        float bv = a.b[l][k];
-        if (l == 0 && a.ctx != nullptr && row < a.B) bv += a.ctx[row * a.ldc + k];
-        hs[((long)l * R + r) * H + k] = bv;
-      }
-  }
-  __syncthreads();
+#define NF_SWEEP_PHASE 1   // stage the tile
+#include "made_sweep_phases.h"
 
   const float* hL = hs + (long)(L - 1) * R * H;
   float ldj = 0.f;
@@ -150,41 +114,13 @@ __global__ __launch_bounds__(NT) void made_sweep_kernel(const SweepArgs a) {
     }
     __syncthreads();
     // ---- hidden units of degree t, layer by layer
-    for (int l = 0; l < L; ++l) {
-      const int u0 = clampi(a.ubeg[l * W2 + t], 0, H);
-      const int u1 = clampi(a.ubeg[l * W2 + t + 1], u0, H);
-      if (u1 == u0) continue;   // block-uniform
-      const int n = l == 0 ? t : clampi(a.ubeg[(l - 1) * W2 + t + 1], 0, H);
-      const float* in = l == 0 ? xs : hs + (long)(l - 1) * R * H;
-      const int ldi = l == 0 ? D : H;
-      float* out = hs + (long)l * R * H;
-      for (int k = u0 + wid; k < u1; k += NW) {
-        const float* w = a.W[l] + (long)k * a.ldw[l];
-        float acc[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = 0.f;
-#pragma unroll 2
-        for (int j = lane; j < n; j += 64) {
-          const float wv = l == 0 ? w[pl[j]] : w[j];
-#pragma unroll
-          for (int r = 0; r < R; ++r) acc[r] = fmaf(wv, in[r * ldi + j], acc[r]);
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          const float sum = nf::wave_sum(acc[r]);
-          if (lane == r) out[r * H + k] = fmaxf(out[r * H + k] + sum, 0.f);
-        }
-      }
-      __syncthreads();
-    }
+#define NF_SWEEP_PHASE 2
+#include "made_sweep_phases.h"
   }
 
   if (tid < R && row0 + tid < a.B) a.ldj[row0 + tid] = ldj;
-  for (int r = 0; r < R; ++r) {
-    const long row = row0 + r;
-    if (row >= a.B) break;
-    for (int p = tid; p < D; p += NT) a.x[row * a.ldx + pl[p]] = xs[r * D + p];
-  }
+#define NF_SWEEP_PHASE 3   // store x
+#include "made_sweep_phases.h"
 }
 
 template <int R>

@@ -1,9 +1,12 @@
 """Timing of one MAF layer's sampling direction (u -> x): the degree-sweep HIP kernel
 (csrc/kernels/made_sweep.hip) and, with ``--baseline``, the sequential loop of D MADE passes it
-replaces, on the same device in the same process.
+replaces, on the same device in the same process. ``--flow dsf --units U`` times the inverse of
+one ``DSFAutoregressive`` layer instead (csrc/kernels/dsf_sweep.hip against the loop of D MADE
+passes and root solves that ``DSFAutoregressive.inverse`` runs when the sweep does not apply).
 
-    python -m vi_normflows_amd.bench.made_sweep_bench [--batch 4096] [--d 256] [--hidden 512]
-        [--layers 1] [--reps 20] [--baseline] [--baseline-reps 3] [--density N]
+    python -m vi_normflows_amd.bench.made_sweep_bench [--flow maf|dsf] [--units 8] [--batch 4096]
+        [--d 256] [--hidden 512] [--layers 1] [--reps 20] [--baseline] [--baseline-reps 3]
+        [--density N]
 
 After a warm-up, the median of ``--reps`` HIP-event timings of the sweep; with ``--baseline`` the
 loop takes turns with it for ``--baseline-reps`` reps (it is D MADE passes: keep that small).
@@ -33,9 +36,25 @@ def sequential_sample(flow, u):
     return x, -ldj_inv
 
 
+def sequential_dsf_inverse(flow, y):
+    """The D-pass loop of ``DSFAutoregressive.inverse`` (what runs when the sweep does not
+    apply)."""
+    from ..ops.dsf import dsf_transform
+
+    z = torch.zeros_like(y)
+    for i in torch.argsort(flow.made.order).tolist():
+        p_i = flow.made(z, None)[:, :, i].contiguous()
+        z[:, i] = dsf_transform(p_i, y[:, i:i + 1].contiguous(), flow.units,
+                                inverse=True)[0][:, 0].to(y.dtype)
+    _, ldj = flow.forward(z, None)
+    return z, -ldj
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--flow", choices=("maf", "dsf"), default="maf")
+    ap.add_argument("--units", type=int, default=8, help="sigmoid units per coordinate (dsf)")
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--d", type=int, default=256)
     ap.add_argument("--hidden", type=int, default=512)
@@ -48,6 +67,7 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("made_sweep_bench: needs a GPU (no CPU fallback)")
     from ..flows.made import MAF
+    from ..flows.naf import DSFAutoregressive
     from ..ops import autoregressive as ar
     from ..ops._ext import native
 
@@ -55,7 +75,8 @@ def main(argv=None):
     dev = torch.device("cuda")
     B, D, H, L = a.batch, a.d, a.hidden, a.layers
     torch.manual_seed(0)
-    flow = MAF(D, H, L).to(dev)
+    dsf = a.flow == "dsf"
+    flow = (DSFAutoregressive(D, a.units, H, L) if dsf else MAF(D, H, L)).to(dev)
     g = torch.Generator(device=dev).manual_seed(0)
     with torch.no_grad():   # well-conditioned, not near-identity: N(0, 1) * 0.7 / sqrt(fan_in)
         for layer in flow.made.layers:
@@ -63,22 +84,28 @@ def main(argv=None):
                                * 0.7 / layer.weight.shape[1] ** 0.5)
             layer.bias.copy_(torch.randn(layer.bias.shape, device=dev, generator=g) * 0.3)
     u = torch.randn(B, D, device=dev, generator=g)
-    rec = {"bench": "made_sweep", "B": B, "D": D, "H": H, "L": L, "reps": a.reps,
-           "rows_per_block": ar.kernel_rows(D, H, L), "device": torch.cuda.get_device_name(0)}
+    rec = {"bench": "dsf_sweep" if dsf else "made_sweep", "B": B, "D": D, "H": H, "L": L,
+           "reps": a.reps, "device": torch.cuda.get_device_name(0),
+           "rows_per_block": (ar.dsf_kernel_rows(D, H, L, a.units) if dsf
+                              else ar.kernel_rows(D, H, L))}
+    if dsf:
+        rec["units"] = a.units
+    run = flow.inverse if dsf else flow
+    sequential = sequential_dsf_inverse if dsf else sequential_sample
     with torch.no_grad():
         assert ar.dispatch(flow, u, None), "shape outside the sweep kernel's limits"
-        fns = {"sweep": lambda: flow(u)}
+        fns = {"sweep": lambda: run(u)}
         if a.baseline:
             for _ in range(3):
-                flow(u)
-            us = alternate({**fns, "sequential": lambda: sequential_sample(flow, u)},
+                run(u)
+            us = alternate({**fns, "sequential": lambda: sequential(flow, u)},
                            a.baseline_reps, warmup=1)
             rec["us_ab"] = {k: round(v, 1) for k, v in us.items()}
             rec["baseline_reps"] = a.baseline_reps
             rec["speedup_vs_sequential"] = round(us["sequential"] / us["sweep"], 1)
             # the loop runs the MADE products in bf16: how far its sample is from the sweep's
             rec["max_abs_diff_vs_sequential"] = float(
-                (flow(u)[0] - sequential_sample(flow, u)[0]).abs().max())
+                (run(u)[0] - sequential(flow, u)[0]).abs().max())
         rec["us"] = round(alternate(fns, a.reps)["sweep"], 1)
         rec["rows_per_s"] = round(B / rec["us"] * 1e6)
         if a.density:

@@ -96,11 +96,17 @@ class DSFAutoregressive(Flow):
 
     @torch.no_grad()
     def inverse(self, y, context=None):
-        """Sequential inverse (D MADE passes, each followed by the root solve of one
-        coordinate); returns ``(z, -ldj)`` with ldj from one forward pass at z. For sampling
-        and checks: it runs without a graph and is not differentiated. The degree sweep of
-        ``ops.autoregressive`` (one masked pass for MAF / IAF) would apply here too, with the
-        root solve as the per-coordinate transform; this layer has not adopted it yet."""
+        """Inverse ``(z, -ldj)``, for sampling and checks: it runs without a graph and is not
+        differentiated. fp32 GPU tensors with a supported MADE (ReLU, 1 .. 4 hidden layers, a
+        bias on every layer, a shape inside the kernel's LDS budget) take the degree sweep of
+        ``ops.autoregressive``: one masked pass with the root solve as the per-coordinate
+        transform, ldj from the same kernel. Every other call (CPU, fp64, other shapes) runs
+        the sequential loop: D MADE passes, each followed by the root solve of one coordinate,
+        and ldj from one forward pass at z."""
+        from ..ops import autoregressive as ar
+
+        if y.is_cuda and ar.supported(self.made, y, context, 3 * self.units):
+            return ar.dsf_sweep_flow(self, y, context)
         z = torch.zeros_like(y)
         for i in torch.argsort(self.made.order).tolist():
             p_i = self.made(z, context)[:, :, i].contiguous()          # [N, 3 units]

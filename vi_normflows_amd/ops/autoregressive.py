@@ -18,8 +18,13 @@ block with its state in LDS; a row's result is bitwise independent of the batch 
 call never falls back to it: a missing native library or a shape outside the kernel's LDS budget
 raises (callers that have another path ask :func:`supported` first).
 
+The inverse of a MADE-conditioned deep sigmoidal flow layer (``DSFAutoregressive.inverse``) is the
+same walk with ``3 units`` outputs per coordinate and the DSF root solve as the transform:
+:func:`dsf_sweep` (``csrc/kernels/dsf_sweep.hip``), :func:`dsf_sweep_composite`,
+:func:`dsf_sweep_flow`.
+
 Not differentiable: ``MAF.forward`` / ``IAF.inverse`` take this path only when nothing needs a
-graph (:func:`dispatch`).
+graph (:func:`dispatch`); ``DSFAutoregressive.inverse`` never builds one.
 """
 from __future__ import annotations
 
@@ -109,18 +114,7 @@ def made_sweep_composite(v, weights, biases, order, kind, *, ctx_bias=None, boun
         s = bs[L][i + D] + h[L - 1][:, :c] @ Ws[L][i + D, :c]
         x[:, i], share = _transform(kind, v[:, i], m, s, bound, gate_bias, scale)
         ldj = ldj + share
-        for l in range(L):
-            u0, u1 = ubeg[l][t], ubeg[l][t + 1]
-            if u1 == u0:
-                continue
-            if l == 0:
-                pre = x[:, idx[:t]] @ Ws[0][u0:u1][:, idx[:t]].T
-                if ctx_bias is not None:
-                    pre = pre + ctx_bias[:, u0:u1].to(v.dtype)
-            else:
-                n = ubeg[l - 1][t + 1]
-                pre = h[l - 1][:, :n] @ Ws[l][u0:u1, :n].T
-            h[l][:, u0:u1] = torch.relu(pre + bs[l][u0:u1])
+        _hidden_step(x, h, Ws, bs, ubeg, idx, t, ctx_bias)
     return x, ldj
 
 
@@ -150,12 +144,7 @@ def made_sweep(v, weights, biases, order, kind, *, ctx_bias=None, bound=5.0, gat
     composite."""
     if kind not in KINDS:
         raise ValueError(f"made_sweep: kind must be one of {sorted(KINDS)}, got {kind!r}")
-    if v.dim() != 2 or len(weights) < 2 or len(weights) != len(biases):
-        raise ValueError("made_sweep: v [B, D] and at least one hidden plus the output layer")
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad
-                                       for t in (v, ctx_bias, *weights, *biases)):
-        raise RuntimeError("made_sweep is not differentiable: detach the inputs or call it under "
-                           "torch.no_grad()")
+    _check_sweep_inputs("made_sweep", v, weights, biases, ctx_bias)
     if not v.is_cuda:
         return made_sweep_composite(v, weights, biases, order, kind, ctx_bias=ctx_bias,
                                     bound=bound, gate_bias=gate_bias, scale=scale, plan=plan)
@@ -170,26 +159,133 @@ def made_sweep(v, weights, biases, order, kind, *, ctx_bias=None, bound=5.0, gat
                            "budget")
     perm, ubeg = (plan or plan_for(D, H, L, order)).on(v.device)
 
-    def rows(t):   # unit inner stride
-        t = t.detach()
-        return t if t.shape[1] == 1 or t.stride(1) == 1 else t.contiguous()
-
     param = {"maf_sample": bound, "iaf_gated": gate_bias, "iaf_affine": scale}[kind]
     x = torch.empty(B, D, device=v.device, dtype=torch.float32)
     ldj = torch.empty(B, device=v.device, dtype=torch.float32)
-    ops.made_sweep(rows(v), [rows(w) for w in weights], [b.detach().contiguous() for b in biases],
-                   perm, ubeg, KINDS[kind], float(param),
-                   None if ctx_bias is None else rows(ctx_bias.float()), x, ldj)
+    ops.made_sweep(_rows(v), [_rows(w) for w in weights],
+                   [b.detach().contiguous() for b in biases], perm, ubeg, KINDS[kind], float(param),
+                   None if ctx_bias is None else _rows(ctx_bias.float()), x, ldj)
     _sweep_launches += 1
     return x, ldj
 
 
-def supported(made, v, context) -> bool:
-    """A MADE and input the sweep handles: ReLU, 1 .. 4 hidden layers, two outputs per input,
-    fp32 everywhere, a context exactly when the MADE projects one, and (GPU) a shape inside the
-    kernel's LDS budget."""
+def _check_sweep_inputs(name, v, weights, biases, ctx_bias):
+    if v.dim() != 2 or len(weights) < 2 or len(weights) != len(biases):
+        raise ValueError(f"{name}: v [B, D] and at least one hidden plus the output layer")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad
+                                       for t in (v, ctx_bias, *weights, *biases)):
+        raise RuntimeError(f"{name} is not differentiable: detach the inputs or call it under "
+                           "torch.no_grad()")
+
+
+def _rows(t):   # unit inner stride
+    t = t.detach()
+    return t if t.shape[1] == 1 or t.stride(1) == 1 else t.contiguous()
+
+
+def _hidden_step(x, h, Ws, bs, ubeg, idx, t, ctx_bias):
+    """The hidden units of degree ``t`` of every layer, in place in ``h``."""
+    for l in range(len(h)):
+        u0, u1 = ubeg[l][t], ubeg[l][t + 1]
+        if u1 == u0:
+            continue
+        if l == 0:
+            pre = x[:, idx[:t]] @ Ws[0][u0:u1][:, idx[:t]].T
+            if ctx_bias is not None:
+                pre = pre + ctx_bias[:, u0:u1].to(x.dtype)
+        else:
+            n = ubeg[l - 1][t + 1]
+            pre = h[l - 1][:, :n] @ Ws[l][u0:u1, :n].T
+        h[l][:, u0:u1] = torch.relu(pre + bs[l][u0:u1])
+
+
+def _check_units(units) -> int:
+    if not 1 <= int(units) <= 32:
+        raise ValueError(f"dsf_sweep: need 1 <= units <= 32, got {units}")
+    return int(units)
+
+
+def dsf_sweep_composite(y, weights, biases, order, units, *, ctx_bias=None, plan=None):
+    """The DSF sweep in torch, in the dtype of ``y`` (weights are cast to it): per coordinate the
+    ``3 units`` outputs over the prefix ``h_L[:c(t)]``, then ``ops.reference.dsf_transform(...,
+    inverse=True)`` of that one coordinate."""
+    from .reference import dsf_transform
+
+    U = _check_units(units)
+    B, D = y.shape
+    L, H = len(weights) - 1, weights[0].shape[0]
+    if weights[L].shape[0] != 3 * U * D:
+        raise ValueError(f"dsf_sweep: the output layer has {weights[L].shape[0]} rows, expected "
+                         f"3 units D = {3 * U * D}")
+    plan = plan or plan_for(D, H, L, order)
+    perm, ubeg = plan.perm.tolist(), plan.ubeg.tolist()
+    Ws = [w.detach().to(y.dtype) for w in weights]
+    bs = [b.detach().to(y.dtype) for b in biases]
+    idx = plan.perm.to(y.device, torch.long)
+    planes = torch.arange(3 * U, device=y.device) * D
+    z = torch.empty_like(y)
+    ldj = y.new_zeros(B)
+    h = [y.new_zeros(B, H) for _ in range(L)]
+    with torch.no_grad():
+        for t in range(1, D + 1):
+            i, c = perm[t - 1], ubeg[L - 1][t]
+            p = bs[L][planes + i] + h[L - 1][:, :c] @ Ws[L][planes + i, :c].T     # [B, 3U]
+            zi, share = dsf_transform(p, y[:, i:i + 1], U, inverse=True)
+            z[:, i] = zi[:, 0]
+            ldj = ldj + share
+            _hidden_step(z, h, Ws, bs, ubeg, idx, t, ctx_bias)
+    return z, ldj
+
+
+def dsf_kernel_supported(D: int, H: int, L: int, units: int) -> bool:
+    """``dsf_sweep_supported`` of the native library: 1 <= units <= 32 and the (D, H, L, units)
+    state of at least one row fits the LDS budget the launcher requests."""
+    return bool(native().dsf_sweep_supported(int(D), int(H), int(L), int(units)))
+
+
+def dsf_kernel_rows(D: int, H: int, L: int, units: int) -> int:
+    """Rows per block the DSF launcher picks for (D, H, L, units); 0 when unsupported."""
+    return int(native().dsf_sweep_rows(int(D), int(H), int(L), int(units)))
+
+
+def dsf_sweep(y, weights, biases, order, units, *, ctx_bias=None, plan=None):
+    """``(z, ldj)`` of the inverse of one MADE-conditioned DSF layer; no-grad.
+
+    ``weights`` / ``biases``: the MADE's hidden layers then its output layer ([3 units D, H],
+    plane-major: row k D + i is plane k of coordinate i; planes [0, units) raw slopes, then
+    shifts, then mixture logits), fp32 and unmasked. ``z_i`` solves
+    ``logit(sum_h w_h sigmoid(a_h z + b_h)) = y_i`` and ``ldj = -sum_i log dy_i/dz_i`` at z.
+    ``order`` / ``ctx_bias`` / ``plan`` as in :func:`made_sweep`. GPU tensors run the HIP kernel
+    (fp32 only, raising outside its limits), CPU tensors the composite."""
+    U = _check_units(units)
+    _check_sweep_inputs("dsf_sweep", y, weights, biases, ctx_bias)
+    if not y.is_cuda:
+        return dsf_sweep_composite(y, weights, biases, order, U, ctx_bias=ctx_bias, plan=plan)
+    global _sweep_launches
+    ops = native()
+    B, D = y.shape
+    L, H = len(weights) - 1, weights[0].shape[0]
+    if y.dtype != torch.float32 or any(t.dtype != torch.float32 for t in (*weights, *biases)):
+        raise RuntimeError("dsf_sweep: the HIP kernel takes fp32 tensors only")
+    if not ops.dsf_sweep_supported(D, H, L, U):
+        raise RuntimeError(f"dsf_sweep: (D, H, L, units) = ({D}, {H}, {L}, {U}) is outside the "
+                           "kernel's LDS budget")
+    perm, ubeg = (plan or plan_for(D, H, L, order)).on(y.device)
+    z = torch.empty(B, D, device=y.device, dtype=torch.float32)
+    ldj = torch.empty(B, device=y.device, dtype=torch.float32)
+    ops.dsf_sweep(_rows(y), [_rows(w) for w in weights], [b.detach().contiguous() for b in biases],
+                  perm, ubeg, U, None if ctx_bias is None else _rows(ctx_bias.float()), z, ldj)
+    _sweep_launches += 1
+    return z, ldj
+
+
+def supported(made, v, context, out_mult: int = 2) -> bool:
+    """A MADE and input the sweep handles: ReLU, 1 .. 4 hidden layers, ``out_mult`` outputs per
+    input (2: MAF / IAF; 3 units: a DSF layer), fp32 everywhere, a context exactly when the MADE
+    projects one, and (GPU) a shape inside the kernel's LDS budget."""
     L = len(made.layers) - 1
-    if not (isinstance(made.act, torch.nn.ReLU) and 1 <= L <= MAX_HIDDEN and made.out_mult == 2):
+    if not (isinstance(made.act, torch.nn.ReLU) and 1 <= L <= MAX_HIDDEN
+            and made.out_mult == out_mult):
         return False
     if v.dim() != 2 or v.dtype != torch.float32 or v.shape[1] != made.dim or v.shape[0] < 1:
         return False
@@ -199,19 +295,45 @@ def supported(made, v, context) -> bool:
         return False
     if context is not None and (context.dim() != 2 or context.shape[0] != v.shape[0]):
         return False
-    return not v.is_cuda or kernel_supported(made.dim, made.layers[0].weight.shape[0], L)
+    if not v.is_cuda:
+        return True
+    H = made.layers[0].weight.shape[0]
+    if out_mult == 2:
+        return kernel_supported(made.dim, H, L)
+    return out_mult % 3 == 0 and dsf_kernel_supported(made.dim, H, L, out_mult // 3)
 
 
 def dispatch(flow, v, context) -> bool:
-    """True when ``MAF.forward`` / ``IAF.inverse`` take the sweep: GPU tensors, a supported MADE,
-    and nothing that needs a graph (grad mode off, or neither the input, the context nor any
+    """True when ``MAF.forward`` / ``IAF.inverse`` / ``DSFAutoregressive.inverse`` take the sweep:
+    GPU tensors, a supported MADE (two outputs per input, or ``3 units`` for the DSF layer), and
+    nothing that needs a graph (grad mode off, or neither the input, the context nor any
     parameter of the flow requires grad)."""
-    if not v.is_cuda or not supported(flow.made, v, context):
+    if not v.is_cuda or not supported(flow.made, v, context, flow.made.out_mult):
         return False
     if not torch.is_grad_enabled():
         return True
     return not (v.requires_grad or (context is not None and context.requires_grad)
                 or any(p.requires_grad for p in flow.parameters()))
+
+
+def _plan_of(made) -> SweepPlan:
+    plan = made.__dict__.get("_sweep_plan")   # cached on the module, like ops.masked.MaskPlan
+    if plan is None:
+        plan = made.__dict__["_sweep_plan"] = plan_for(
+            made.dim, made.layers[0].weight.shape[0], len(made.layers) - 1, made.order)
+    return plan
+
+
+def dsf_sweep_flow(flow, y, context=None):
+    """The sweep of a ``DSFAutoregressive`` layer (inverse, y -> z): the ``(z, -ldj)`` that
+    ``DSFAutoregressive.inverse`` returns."""
+    made = flow.made
+    with torch.no_grad():
+        ctx_bias = None
+        if made.ctx is not None and context is not None:
+            ctx_bias = made.ctx(context)
+        return dsf_sweep(y, [l.weight for l in made.layers], [l.bias for l in made.layers],
+                         made.order, flow.units, ctx_bias=ctx_bias, plan=_plan_of(made))
 
 
 def made_sweep_flow(flow, v, context=None):
@@ -227,13 +349,9 @@ def made_sweep_flow(flow, v, context=None):
         kw = {"gate_bias": flow.gate_bias, "scale": flow.scale}
     else:
         raise TypeError(f"made_sweep_flow: expected a MAF or IAF layer, got {type(flow).__name__}")
-    plan = made.__dict__.get("_sweep_plan")   # cached on the module, like ops.masked.MaskPlan
-    if plan is None:
-        plan = made.__dict__["_sweep_plan"] = plan_for(
-            made.dim, made.layers[0].weight.shape[0], len(made.layers) - 1, made.order)
     with torch.no_grad():
         ctx_bias = None
         if made.ctx is not None and context is not None:
             ctx_bias = made.ctx(context)
         return made_sweep(v, [l.weight for l in made.layers], [l.bias for l in made.layers],
-                          made.order, kind, ctx_bias=ctx_bias, plan=plan, **kw)
+                          made.order, kind, ctx_bias=ctx_bias, plan=_plan_of(made), **kw)
