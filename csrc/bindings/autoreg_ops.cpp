@@ -1,6 +1,7 @@
 // TORCH_LIBRARY fragment for the autoregressive degree sweeps: MAF sampling and the IAF inverse
-// (made_sweep.hip) and the inverse of a MADE-conditioned DSF layer (dsf_sweep.hip) in one masked
-// pass. Not differentiable.
+// (made_sweep.hip), the inverse of a MADE-conditioned DSF layer (dsf_sweep.hip) and the sequential
+// direction of a MADE-conditioned spline layer (rqs_sweep.hip) in one masked pass. Not
+// differentiable.
 #include <torch/library.h>
 #include <ATen/ATen.h>
 
@@ -106,6 +107,22 @@ void dsf_sweep(const at::Tensor& y, at::TensorList weights, at::TensorList biase
   nf_launch_dsf_sweep(s, (int)units, cur_stream());
 }
 
+// y [B, D] -> z = x with T(z) = y, ldj of the inverse of a spline layer with `bins` bins on
+// (-bound, bound); the output layer is [(3 bins - 1) D, H] plane-major (MADE(out_mult = 3 bins - 1)).
+void rqs_sweep(const at::Tensor& y, at::TensorList weights, at::TensorList biases,
+               const at::Tensor& perm, const at::Tensor& ubeg, int64_t bins, double bound,
+               const c10::optional<at::Tensor>& ctx_bias, const at::Tensor& x,
+               const at::Tensor& ldj) {
+  TORCH_CHECK(bins >= 2 && bins <= 32, "rqs_sweep: need 2 <= bins <= 32, got ", bins);
+  TORCH_CHECK(bound > 0 && (float)bound > 0.f, "rqs_sweep: need bound > 0, got ", bound);
+  NfMadeSweep s =
+      sweep_args("rqs_sweep", y, weights, biases, perm, ubeg, 3 * bins - 1, ctx_bias, x, ldj);
+  TORCH_CHECK(nf_rqs_sweep_rows(s.D, s.H, s.L, (int)bins) > 0, "rqs_sweep: (D, H, L, K) = (", s.D,
+              ", ", s.H, ", ", s.L, ", ", bins,
+              ") exceeds the kernel's LDS budget (rqs_sweep_supported)");
+  nf_launch_rqs_sweep(s, (int)bins, (float)bound, cur_stream());
+}
+
 // rows per block for (D, H, L); 0 when the shape does not fit
 int64_t made_sweep_rows(int64_t D, int64_t H, int64_t L) {
   if (D < 1 || H < 1 || L < 1 || D >= (1 << 24) || H >= (1 << 24) || L > NF_MADE_SWEEP_MAX_HIDDEN)
@@ -127,6 +144,18 @@ bool dsf_sweep_supported(int64_t D, int64_t H, int64_t L, int64_t U) {
   return dsf_sweep_rows(D, H, L, U) > 0;
 }
 
+// rows per block for (D, H, L, K); 0 when the shape does not fit or K is out of range
+int64_t rqs_sweep_rows(int64_t D, int64_t H, int64_t L, int64_t K) {
+  if (D < 1 || H < 1 || L < 1 || D >= (1 << 24) || H >= (1 << 24) ||
+      L > NF_MADE_SWEEP_MAX_HIDDEN || K < 2 || K > 32)
+    return 0;
+  return nf_rqs_sweep_rows((int)D, (int)H, (int)L, (int)K);
+}
+
+bool rqs_sweep_supported(int64_t D, int64_t H, int64_t L, int64_t K) {
+  return rqs_sweep_rows(D, H, L, K) > 0;
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(vinf, m) {
@@ -138,9 +167,14 @@ TORCH_LIBRARY_FRAGMENT(vinf, m) {
         "int units, Tensor? ctx_bias, Tensor(a!) x, Tensor(b!) ldj) -> ()");
   m.def("dsf_sweep_rows(int D, int H, int L, int U) -> int", &dsf_sweep_rows);
   m.def("dsf_sweep_supported(int D, int H, int L, int U) -> bool", &dsf_sweep_supported);
+  m.def("rqs_sweep(Tensor y, Tensor[] weights, Tensor[] biases, Tensor perm, Tensor ubeg, "
+        "int bins, float bound, Tensor? ctx_bias, Tensor(a!) x, Tensor(b!) ldj) -> ()");
+  m.def("rqs_sweep_rows(int D, int H, int L, int K) -> int", &rqs_sweep_rows);
+  m.def("rqs_sweep_supported(int D, int H, int L, int K) -> bool", &rqs_sweep_supported);
 }
 
 TORCH_LIBRARY_IMPL(vinf, CUDA, m) {
   m.impl("made_sweep", &made_sweep);
   m.impl("dsf_sweep", &dsf_sweep);
+  m.impl("rqs_sweep", &rqs_sweep);
 }

@@ -401,3 +401,13 @@ void nf_launch_made_sweep(const NfMadeSweep& s, hipStream_t stream);
 // rows per block for (D, H, L, U); 0 = the shape is not supported
 int nf_dsf_sweep_rows(int D, int H, int L, int U);
 void nf_launch_dsf_sweep(const NfMadeSweep& s, int U, hipStream_t stream);
+
+// rqs_sweep.hip: the sequential direction of a MADE-conditioned rational-quadratic spline layer
+// (y -> z with T(z) = y) as one degree sweep. The tensors are those of NfMadeSweep (v = y, x = z;
+// kind and param unused) except the output layer: Wo [(3K - 1) D, H] / bo [(3K - 1) D] plane-major
+// (row k D + i is plane k of coordinate i; planes [0, K) unnormalised widths, [K, 2K) heights,
+// [2K, 3K - 1) interior derivatives), 2 <= K <= 32 bins on (-bound, bound), bound > 0. ldj [B] is
+// minus sum_i log dy_i/dz_i at the recovered z.
+// rows per block for (D, H, L, K); 0 = the shape is not supported
+int nf_rqs_sweep_rows(int D, int H, int L, int K);
+void nf_launch_rqs_sweep(const NfMadeSweep& s, int K, float bound, hipStream_t stream);

@@ -1,5 +1,6 @@
 // Shared frame of the degree-sweep kernels (made_sweep.hip: MAF sampling / IAF inverse with two
-// outputs per coordinate; dsf_sweep.hip: the DSF inverse with 3U outputs and a root solve): the
+// outputs per coordinate; dsf_sweep.hip: the DSF inverse with 3U outputs and a root solve;
+// rqs_sweep.hip: the spline inverse with 3K - 1 outputs and a closed-form transform): the
 // kernel arguments, the block geometry and the LDS budget. The staging of a row tile, the
 // hidden-unit phase of one step and the final store are the body fragments of
 // made_sweep_phases.h; a kernel supplies the output phase and the transform of the coordinate of

@@ -1,4 +1,5 @@
-// The phases both degree-sweep kernels run verbatim (made_sweep.hip, dsf_sweep.hip). This file is
+// The phases the degree-sweep kernels run verbatim (made_sweep.hip, dsf_sweep.hip, rqs_sweep.hip).
+// This file is
 // a BODY FRAGMENT: it is included inside a kernel, once per phase, with NF_SWEEP_PHASE set to
 //   1  stage:  clamped perm into LDS, then v in degree order and every hidden layer pre-filled
 //              with bias (+ context projection); ends with a barrier

@@ -2,11 +2,13 @@
 (csrc/kernels/made_sweep.hip) and, with ``--baseline``, the sequential loop of D MADE passes it
 replaces, on the same device in the same process. ``--flow dsf --units U`` times the inverse of
 one ``DSFAutoregressive`` layer instead (csrc/kernels/dsf_sweep.hip against the loop of D MADE
-passes and root solves that ``DSFAutoregressive.inverse`` runs when the sweep does not apply).
+passes and root solves that ``DSFAutoregressive.inverse`` runs when the sweep does not apply);
+``--flow rqs --bins K`` the sequential direction of one ``RQSAutoregressive`` layer
+(csrc/kernels/rqs_sweep.hip against the loop of D MADE passes and spline inverses).
 
-    python -m vi_normflows_amd.bench.made_sweep_bench [--flow maf|dsf] [--units 8] [--batch 4096]
-        [--d 256] [--hidden 512] [--layers 1] [--reps 20] [--baseline] [--baseline-reps 3]
-        [--density N]
+    python -m vi_normflows_amd.bench.made_sweep_bench [--flow maf|dsf|rqs] [--units 8] [--bins 8]
+        [--batch 4096] [--d 256] [--hidden 512] [--layers 1] [--reps 20] [--baseline]
+        [--baseline-reps 3] [--density N]
 
 After a warm-up, the median of ``--reps`` HIP-event timings of the sweep; with ``--baseline`` the
 loop takes turns with it for ``--baseline-reps`` reps (it is D MADE passes: keep that small).
@@ -50,11 +52,26 @@ def sequential_dsf_inverse(flow, y):
     return z, -ldj
 
 
+def sequential_rqs_inverse(flow, y):
+    """The D-pass loop of ``RQSAutoregressive``'s sequential direction (what runs when the sweep
+    does not apply)."""
+    from ..ops.spline import rqs_transform
+
+    z = torch.zeros_like(y)
+    for i in torch.argsort(flow.made.order).tolist():
+        p_i = flow.made(z, None)[:, :, i].contiguous()
+        z[:, i] = rqs_transform(p_i, y[:, i:i + 1].contiguous(), flow.bins, flow.bound,
+                                inverse=True)[0][:, 0].to(y.dtype)
+    _, ldj = flow.forward(z, None)
+    return z, -ldj
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--flow", choices=("maf", "dsf"), default="maf")
+    ap.add_argument("--flow", choices=("maf", "dsf", "rqs"), default="maf")
     ap.add_argument("--units", type=int, default=8, help="sigmoid units per coordinate (dsf)")
+    ap.add_argument("--bins", type=int, default=8, help="spline bins per coordinate (rqs)")
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--d", type=int, default=256)
     ap.add_argument("--hidden", type=int, default=512)
@@ -68,6 +85,7 @@ def main(argv=None):
         raise SystemExit("made_sweep_bench: needs a GPU (no CPU fallback)")
     from ..flows.made import MAF
     from ..flows.naf import DSFAutoregressive
+    from ..flows.spline import RQSAutoregressive
     from ..ops import autoregressive as ar
     from ..ops._ext import native
 
@@ -75,8 +93,11 @@ def main(argv=None):
     dev = torch.device("cuda")
     B, D, H, L = a.batch, a.d, a.hidden, a.layers
     torch.manual_seed(0)
-    dsf = a.flow == "dsf"
-    flow = (DSFAutoregressive(D, a.units, H, L) if dsf else MAF(D, H, L)).to(dev)
+    dsf, rqs = a.flow == "dsf", a.flow == "rqs"
+    if rqs:
+        flow = RQSAutoregressive(D, a.bins, hidden=H, n_hidden=L).to(dev)
+    else:
+        flow = (DSFAutoregressive(D, a.units, H, L) if dsf else MAF(D, H, L)).to(dev)
     g = torch.Generator(device=dev).manual_seed(0)
     with torch.no_grad():   # well-conditioned, not near-identity: N(0, 1) * 0.7 / sqrt(fan_in)
         for layer in flow.made.layers:
@@ -84,14 +105,18 @@ def main(argv=None):
                                * 0.7 / layer.weight.shape[1] ** 0.5)
             layer.bias.copy_(torch.randn(layer.bias.shape, device=dev, generator=g) * 0.3)
     u = torch.randn(B, D, device=dev, generator=g)
-    rec = {"bench": "dsf_sweep" if dsf else "made_sweep", "B": B, "D": D, "H": H, "L": L,
-           "reps": a.reps, "device": torch.cuda.get_device_name(0),
-           "rows_per_block": (ar.dsf_kernel_rows(D, H, L, a.units) if dsf
+    rec = {"bench": "rqs_sweep" if rqs else "dsf_sweep" if dsf else "made_sweep", "B": B, "D": D,
+           "H": H, "L": L, "reps": a.reps, "device": torch.cuda.get_device_name(0),
+           "rows_per_block": (ar.rqs_kernel_rows(D, H, L, a.bins) if rqs
+                              else ar.dsf_kernel_rows(D, H, L, a.units) if dsf
                               else ar.kernel_rows(D, H, L))}
     if dsf:
         rec["units"] = a.units
-    run = flow.inverse if dsf else flow
-    sequential = sequential_dsf_inverse if dsf else sequential_sample
+    if rqs:
+        rec["bins"] = a.bins
+    run = flow.inverse if dsf or rqs else flow
+    sequential = (sequential_rqs_inverse if rqs else sequential_dsf_inverse if dsf
+                  else sequential_sample)
     with torch.no_grad():
         assert ar.dispatch(flow, u, None), "shape outside the sweep kernel's limits"
         fns = {"sweep": lambda: run(u)}

@@ -1,5 +1,6 @@
 """Normalizing-flow layers: planar, radial, diagonal affine, RealNVP coupling, MADE/IAF/MAF,
-rational-quadratic spline coupling, Sylvester, neural autoregressive (deep sigmoidal)."""
+rational-quadratic spline (coupling and autoregressive), Sylvester, neural autoregressive (deep
+sigmoidal)."""
 from .affine import DiagAffine
 from .base import Flow, FlowDistribution, FlowSequence, Permute, Reverse
 from .coupling import AffineCoupling, RealNVP, coupling_transform
@@ -11,7 +12,7 @@ from .planar import (AmortizedPlanar, Planar, PlanarStack, get_uhat, m, planar_f
 from .radial import (AmortizedRadial, Radial, RadialStack, radial_params, radial_stack,
                      radial_stack_inverse, radial_stack_inverse_reference,
                      radial_stack_reference)
-from .spline import NeuralSplineFlow, RQSCoupling
+from .spline import MaskedSplineFlow, NeuralSplineFlow, RQSAutoregressive, RQSCoupling
 from .sylvester import AmortizedSylvester, SylvesterStack
 
 __all__ = [
@@ -20,7 +21,8 @@ __all__ = [
     "made_degrees", "made_masks", "Planar", "PlanarStack", "AmortizedPlanar", "get_uhat", "m",
     "planar_flow", "planar_stack", "planar_stack_reference", "Radial", "RadialStack",
     "AmortizedRadial", "radial_params", "radial_stack", "radial_stack_reference",
-    "RQSCoupling", "NeuralSplineFlow", "SylvesterStack", "AmortizedSylvester",
+    "RQSCoupling", "NeuralSplineFlow", "RQSAutoregressive", "MaskedSplineFlow",
+    "SylvesterStack", "AmortizedSylvester",
     "DSFCoupling", "DSFAutoregressive", "NeuralAutoregressiveFlow",
     "planar_stack_inverse", "planar_stack_inverse_reference", "radial_stack_inverse",
     "radial_stack_inverse_reference",

@@ -1,4 +1,5 @@
-"""Rational-quadratic spline coupling layers (Durkan et al. 2019, "Neural Spline Flows").
+"""Rational-quadratic spline layers (Durkan et al. 2019, "Neural Spline Flows"): couplings and
+MADE-conditioned autoregressive layers.
 
 y_a = x_a, y_b = RQS(x_b; NN(x_a)): every coordinate of the transformed half goes through its
 own monotone K-bin rational-quadratic spline on (-bound, bound), the identity outside, whose
@@ -8,9 +9,14 @@ form, so the same layer serves VI (forward) and density estimation (``log_prob``
 ``inverse``). The conditioner's last layer starts at zero, which makes every spline the
 identity with ldj 0 at initialisation.
 
+``RQSAutoregressive`` / ``MaskedSplineFlow`` are RQ-NSF (AR) of the same paper: the spline's
+parameters come from a MADE, so one direction is one pass and the other solves coordinate by
+coordinate in degree order - on the GPU one degree sweep (``csrc/kernels/rqs_sweep.hip``,
+``ops/autoregressive.py``) instead of D MADE passes.
+
 Not in the reference. The element-wise part runs in the fused HIP kernels of
-``csrc/kernels/spline.hip`` on the GPU (``ops/spline.py``); conditioners are the same
-``MfmaLinear`` MLPs as the affine couplings'.
+``csrc/kernels/spline.hip`` on the GPU (``ops/spline.py``); the couplings' conditioners are the
+same ``MfmaLinear`` MLPs as the affine couplings'.
 """
 from __future__ import annotations
 
@@ -18,8 +24,9 @@ import torch
 from torch import nn
 
 from ..ops.spline import rqs_transform
-from .base import Flow
+from .base import Flow, Reverse
 from .coupling import mlp
+from .made import MADE
 
 
 class RQSCoupling(Flow):
@@ -76,6 +83,113 @@ class NeuralSplineFlow(Flow):
         self.layers = nn.ModuleList(
             RQSCoupling(dim, bins, bound, hidden, n_hidden, parity=i % 2, context_dim=context_dim)
             for i in range(n_layers))
+        self.uses_context = context_dim > 0
+
+    def forward(self, x, context=None):
+        ldj = torch.zeros(x.shape[0], device=x.device)
+        for f in self.layers:
+            x, l = f(x, context)
+            ldj = ldj + l
+        return x, ldj
+
+    def inverse(self, y, context=None):
+        ldj = torch.zeros(y.shape[0], device=y.device)
+        for f in reversed(self.layers):
+            y, l = f.inverse(y, context)
+            ldj = ldj + l
+        return y, ldj
+
+
+class RQSAutoregressive(Flow):
+    """MADE-conditioned spline layer: MAF / IAF with the affine transformer replaced by the
+    rational-quadratic spline. ``T(x) = RQS(x; MADE(x))`` is one differentiable pass; the other
+    direction solves ``T(z) = y`` coordinate by coordinate in degree order, without a graph.
+
+    ``density=False`` (VI, like ``IAF`` / ``DSFAutoregressive``): ``forward`` is the one-pass
+    ``T`` and ``inverse`` the sequential solve. ``density=True`` (like ``MAF``): ``inverse`` is the
+    one-pass ``T``, so ``FlowDistribution.log_prob`` trains by maximum likelihood in one pass, and
+    ``forward`` is the sequential solve used for sampling. Either method returns the log|det| of
+    the map it applies: ``ldj_T(x)`` with ``T(x)``, ``-ldj_T(z)`` with the solve. The MADE's last
+    layer starts small (1e-2 of its default), so the layer starts near the identity."""
+
+    invertible = True
+
+    def __init__(self, dim: int, bins: int = 8, bound: float = 3.0, hidden: int = 64,
+                 n_hidden: int = 1, context_dim: int = 0, reverse: bool = False,
+                 density: bool = False):
+        super().__init__()
+        if not 2 <= bins <= 32:
+            raise ValueError(f"RQSAutoregressive: need 2 <= bins <= 32, got {bins}")
+        if not bound > 0:
+            raise ValueError(f"RQSAutoregressive: need bound > 0, got {bound}")
+        self.dim, self.bins, self.bound = dim, int(bins), float(bound)
+        self.density = bool(density)
+        order = torch.arange(dim, 0, -1) if reverse else None
+        self.made = MADE(dim, hidden, n_hidden, 3 * self.bins - 1, context_dim, order)
+        self.uses_context = context_dim > 0
+
+    def _params(self, x, context):
+        return self.made(x, context).reshape(x.shape[0], (3 * self.bins - 1) * self.dim)
+
+    def _one_pass(self, x, context=None):
+        """``(T(x), ldj_T(x))``, differentiable."""
+        from ..ops import made_fused
+
+        if made_fused.supported(self.made, x, context):   # GPU: the kernels read the bf16 output
+            return made_fused.rqs_autoregressive(self, x, context)
+        y, ldj = rqs_transform(self._params(x, context), x, self.bins, self.bound)
+        return y.to(x.dtype), ldj
+
+    @torch.no_grad()
+    def _sequential(self, y, context=None):
+        """``(z, -ldj_T(z))`` with ``T(z) = y``, for sampling and checks: it runs without a graph
+        and is not differentiated. fp32 GPU tensors with a supported MADE (ReLU, 1 .. 4 hidden
+        layers, a bias on every layer, a shape inside the kernel's LDS budget) take the degree
+        sweep of ``ops.autoregressive``: one masked pass with the closed-form spline inverse as
+        the per-coordinate transform, ldj from the same kernel. Every other call (CPU, fp64,
+        other shapes) runs the sequential loop: D MADE passes, each followed by the spline
+        inverse of one coordinate, and ldj from one one-pass evaluation at z."""
+        from ..ops import autoregressive as ar
+
+        if y.is_cuda and ar.supported(self.made, y, context, 3 * self.bins - 1):
+            return ar.rqs_sweep_flow(self, y, context)
+        z = torch.zeros_like(y)
+        for i in torch.argsort(self.made.order).tolist():
+            p_i = self.made(z, context)[:, :, i].contiguous()          # [N, 3 bins - 1]
+            z[:, i] = rqs_transform(p_i, y[:, i:i + 1].contiguous(), self.bins, self.bound,
+                                    inverse=True)[0][:, 0].to(y.dtype)
+        _, ldj = self._one_pass(z, context)
+        return z, -ldj
+
+    def forward(self, x, context=None):
+        if self.density:
+            return self._sequential(x, context)
+        return self._one_pass(x, context)
+
+    def inverse(self, y, context=None):
+        if self.density:
+            return self._one_pass(y, context)
+        return self._sequential(y, context)
+
+
+class MaskedSplineFlow(Flow):
+    """Stack of ``RQSAutoregressive`` layers with the coordinate order reversed between them
+    (RQ-NSF (AR)); ``density`` as in the layer."""
+
+    invertible = True
+
+    def __init__(self, dim: int, n_layers: int = 4, bins: int = 8, bound: float = 3.0,
+                 hidden: int = 64, n_hidden: int = 1, context_dim: int = 0,
+                 density: bool = False):
+        super().__init__()
+        layers = []
+        for i in range(n_layers):
+            layers.append(RQSAutoregressive(dim, bins, bound, hidden, n_hidden, context_dim,
+                                            density=density))
+            if i < n_layers - 1:
+                layers.append(Reverse())
+        self.density = bool(density)
+        self.layers = nn.ModuleList(layers)
         self.uses_context = context_dim > 0
 
     def forward(self, x, context=None):

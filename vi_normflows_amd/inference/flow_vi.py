@@ -49,6 +49,12 @@ def build_flow(kind: str, dim: int, K: int, **kw):
 
         return NeuralSplineFlow(dim, n_layers=K, hidden=kw.get("hidden", 64),
                                 bins=kw.get("bins", 8), bound=kw.get("bound", 4.0))
+    if kind == "nsf-ar":
+        from ..flows.spline import MaskedSplineFlow
+
+        return MaskedSplineFlow(dim, n_layers=K, bins=kw.get("bins", 8),
+                                bound=kw.get("bound", 3.0), hidden=kw.get("hidden", 64),
+                                density=kw.get("density", False))
     if kind == "sylvester":
         from ..flows.sylvester import SylvesterStack
 

@@ -23,8 +23,14 @@ same walk with ``3 units`` outputs per coordinate and the DSF root solve as the 
 :func:`dsf_sweep` (``csrc/kernels/dsf_sweep.hip``), :func:`dsf_sweep_composite`,
 :func:`dsf_sweep_flow`.
 
+The sequential direction of a MADE-conditioned rational-quadratic spline layer
+(``RQSAutoregressive``) is the walk with ``3 bins - 1`` outputs per coordinate and the closed-form
+spline inverse as the transform: :func:`rqs_sweep` (``csrc/kernels/rqs_sweep.hip``),
+:func:`rqs_sweep_composite`, :func:`rqs_sweep_flow`.
+
 Not differentiable: ``MAF.forward`` / ``IAF.inverse`` take this path only when nothing needs a
-graph (:func:`dispatch`); ``DSFAutoregressive.inverse`` never builds one.
+graph (:func:`dispatch`); ``DSFAutoregressive.inverse`` and the sequential direction of
+``RQSAutoregressive`` never build one.
 """
 from __future__ import annotations
 
@@ -279,9 +285,100 @@ def dsf_sweep(y, weights, biases, order, units, *, ctx_bias=None, plan=None):
     return z, ldj
 
 
+def _check_bins(bins, bound) -> tuple:
+    if not 2 <= int(bins) <= 32:
+        raise ValueError(f"rqs_sweep: need 2 <= bins <= 32, got {bins}")
+    if not float(bound) > 0:
+        raise ValueError(f"rqs_sweep: need bound > 0, got {bound}")
+    return int(bins), float(bound)
+
+
+def _check_rqs_rows(weights, K, D):
+    if weights[-1].shape[0] != (3 * K - 1) * D:
+        raise ValueError(f"rqs_sweep: the output layer has {weights[-1].shape[0]} rows, expected "
+                         f"(3 bins - 1) D = {(3 * K - 1) * D}")
+
+
+def rqs_sweep_composite(y, weights, biases, order, bins, bound, *, ctx_bias=None, plan=None):
+    """The spline sweep in torch, in the dtype of ``y`` (weights are cast to it): per coordinate
+    the ``3 bins - 1`` outputs over the prefix ``h_L[:c(t)]``, then
+    ``ops.reference.rqs_transform(..., inverse=True)`` of that one coordinate."""
+    from .reference import rqs_transform
+
+    K, bound = _check_bins(bins, bound)
+    B, D = y.shape
+    L, H = len(weights) - 1, weights[0].shape[0]
+    _check_rqs_rows(weights, K, D)
+    plan = plan or plan_for(D, H, L, order)
+    perm, ubeg = plan.perm.tolist(), plan.ubeg.tolist()
+    Ws = [w.detach().to(y.dtype) for w in weights]
+    bs = [b.detach().to(y.dtype) for b in biases]
+    idx = plan.perm.to(y.device, torch.long)
+    planes = torch.arange(3 * K - 1, device=y.device) * D
+    z = torch.empty_like(y)
+    ldj = y.new_zeros(B)
+    h = [y.new_zeros(B, H) for _ in range(L)]
+    with torch.no_grad():
+        for t in range(1, D + 1):
+            i, c = perm[t - 1], ubeg[L - 1][t]
+            p = bs[L][planes + i] + h[L - 1][:, :c] @ Ws[L][planes + i, :c].T     # [B, 3K - 1]
+            zi, share = rqs_transform(p, y[:, i:i + 1], K, bound, inverse=True)
+            z[:, i] = zi[:, 0]
+            ldj = ldj + share
+            _hidden_step(z, h, Ws, bs, ubeg, idx, t, ctx_bias)
+    return z, ldj
+
+
+def rqs_kernel_supported(D: int, H: int, L: int, bins: int) -> bool:
+    """``rqs_sweep_supported`` of the native library: 2 <= bins <= 32 and the (D, H, L, bins)
+    state of at least one row fits the LDS budget the launcher requests."""
+    return bool(native().rqs_sweep_supported(int(D), int(H), int(L), int(bins)))
+
+
+def rqs_kernel_rows(D: int, H: int, L: int, bins: int) -> int:
+    """Rows per block the spline launcher picks for (D, H, L, bins); 0 when unsupported."""
+    return int(native().rqs_sweep_rows(int(D), int(H), int(L), int(bins)))
+
+
+def rqs_sweep(y, weights, biases, order, bins, bound, *, ctx_bias=None, plan=None):
+    """``(z, ldj)`` of the sequential direction of one MADE-conditioned spline layer; no-grad.
+
+    ``weights`` / ``biases``: the MADE's hidden layers then its output layer ([(3 bins - 1) D, H],
+    plane-major: row k D + i is plane k of coordinate i; planes [0, bins) unnormalised widths,
+    then heights, then the bins - 1 interior derivatives), fp32 and unmasked. ``z_i`` solves
+    ``RQS(z_i; p_i(z)) = y_i`` on (-bound, bound) and is ``y_i`` outside;
+    ``ldj = -sum_i log dy_i/dz_i`` at z. ``order`` / ``ctx_bias`` / ``plan`` as in
+    :func:`made_sweep`. GPU tensors run the HIP kernel (fp32 only, raising outside its limits),
+    CPU tensors the composite."""
+    K, bound = _check_bins(bins, bound)
+    _check_sweep_inputs("rqs_sweep", y, weights, biases, ctx_bias)
+    _check_rqs_rows(weights, K, y.shape[1])
+    if not y.is_cuda:
+        return rqs_sweep_composite(y, weights, biases, order, K, bound, ctx_bias=ctx_bias,
+                                   plan=plan)
+    global _sweep_launches
+    ops = native()
+    B, D = y.shape
+    L, H = len(weights) - 1, weights[0].shape[0]
+    if y.dtype != torch.float32 or any(t.dtype != torch.float32 for t in (*weights, *biases)):
+        raise RuntimeError("rqs_sweep: the HIP kernel takes fp32 tensors only")
+    if not ops.rqs_sweep_supported(D, H, L, K):
+        raise RuntimeError(f"rqs_sweep: (D, H, L, bins) = ({D}, {H}, {L}, {K}) is outside the "
+                           "kernel's LDS budget")
+    perm, ubeg = (plan or plan_for(D, H, L, order)).on(y.device)
+    z = torch.empty(B, D, device=y.device, dtype=torch.float32)
+    ldj = torch.empty(B, device=y.device, dtype=torch.float32)
+    ops.rqs_sweep(_rows(y), [_rows(w) for w in weights], [b.detach().contiguous() for b in biases],
+                  perm, ubeg, K, bound, None if ctx_bias is None else _rows(ctx_bias.float()),
+                  z, ldj)
+    _sweep_launches += 1
+    return z, ldj
+
+
 def supported(made, v, context, out_mult: int = 2) -> bool:
     """A MADE and input the sweep handles: ReLU, 1 .. 4 hidden layers, ``out_mult`` outputs per
-    input (2: MAF / IAF; 3 units: a DSF layer), fp32 everywhere, a context exactly when the MADE
+    input (2: MAF / IAF; 3 units: a DSF layer; 3 bins - 1: a spline layer - never a multiple of 3,
+    and 2 stays the affine case), fp32 everywhere, a context exactly when the MADE
     projects one, and (GPU) a shape inside the kernel's LDS budget."""
     L = len(made.layers) - 1
     if not (isinstance(made.act, torch.nn.ReLU) and 1 <= L <= MAX_HIDDEN
@@ -300,12 +397,15 @@ def supported(made, v, context, out_mult: int = 2) -> bool:
     H = made.layers[0].weight.shape[0]
     if out_mult == 2:
         return kernel_supported(made.dim, H, L)
+    if out_mult % 3 == 2 and out_mult >= 5:
+        return rqs_kernel_supported(made.dim, H, L, (out_mult + 1) // 3)
     return out_mult % 3 == 0 and dsf_kernel_supported(made.dim, H, L, out_mult // 3)
 
 
 def dispatch(flow, v, context) -> bool:
-    """True when ``MAF.forward`` / ``IAF.inverse`` / ``DSFAutoregressive.inverse`` take the sweep:
-    GPU tensors, a supported MADE (two outputs per input, or ``3 units`` for the DSF layer), and
+    """True when ``MAF.forward`` / ``IAF.inverse`` / ``DSFAutoregressive.inverse`` / the sequential
+    direction of ``RQSAutoregressive`` take the sweep: GPU tensors, a supported MADE (two outputs
+    per input, ``3 units`` for the DSF layer, ``3 bins - 1`` for the spline layer), and
     nothing that needs a graph (grad mode off, or neither the input, the context nor any
     parameter of the flow requires grad)."""
     if not v.is_cuda or not supported(flow.made, v, context, flow.made.out_mult):
@@ -334,6 +434,19 @@ def dsf_sweep_flow(flow, y, context=None):
             ctx_bias = made.ctx(context)
         return dsf_sweep(y, [l.weight for l in made.layers], [l.bias for l in made.layers],
                          made.order, flow.units, ctx_bias=ctx_bias, plan=_plan_of(made))
+
+
+def rqs_sweep_flow(layer, y, context=None):
+    """The sweep of an ``RQSAutoregressive`` layer (y -> z with T(z) = y): the ``(z, -ldj_T(z))``
+    its sequential direction returns."""
+    made = layer.made
+    with torch.no_grad():
+        ctx_bias = None
+        if made.ctx is not None and context is not None:
+            ctx_bias = made.ctx(context)
+        return rqs_sweep(y, [l.weight for l in made.layers], [l.bias for l in made.layers],
+                         made.order, layer.bins, layer.bound, ctx_bias=ctx_bias,
+                         plan=_plan_of(made))
 
 
 def made_sweep_flow(flow, v, context=None):

@@ -19,8 +19,9 @@ For an IAF layer (``iaf_gated``) the gated update ``y = m + sigmoid(s + b)(z - m
 log-det run in ``csrc/kernels/maf.hip`` (``iaf_gate_fwd/bwd``) straight on the MADE's bf16
 output; its backward writes the bf16 ``[dm | ds]`` operand of the masked GEMMs and the direct
 ``dz`` path, onto which the input-gradient GEMM accumulates the MADE path. MAF's density
-direction (``maf_inverse``) and the MADE-conditioned deep sigmoidal flow layer
-(``dsf_autoregressive``, ``csrc/kernels/dsf.hip``) are built the same way.
+direction (``maf_inverse``), the MADE-conditioned deep sigmoidal flow layer
+(``dsf_autoregressive``, ``csrc/kernels/dsf.hip``) and the MADE-conditioned spline layer
+(``rqs_autoregressive``, ``csrc/kernels/spline.hip``) are built the same way.
 
 Reference parity: the IAF VAE of ``SURVEY.md`` config 4 (the reference's planar-flow VAE
 ``src/learning_mnist.py`` with IAF layers, Kingma et al. 2016); numerics are pinned against the
@@ -330,4 +331,47 @@ def dsf_autoregressive(layer, z, context=None):
     made = layer.made
     has_ctx = made.ctx is not None and context is not None
     return _DSFAutoregressiveFn.apply(made, layer.units, z.contiguous(),
+                                      context if has_ctx else None, *_params(made, has_ctx))
+
+
+class _RQSAutoregressiveFn(torch.autograd.Function):
+    """MADE-conditioned rational-quadratic spline layer (the one-pass direction of
+    ``flows.spline.RQSAutoregressive``): the fused MADE, then ``rqs_fwd`` straight on its bf16
+    plane-major [N, (3 bins - 1) D] output and, backward, ``rqs_bwd`` writing the bf16 operand of
+    the masked GEMMs and the direct ``dx`` path (csrc/kernels/spline.hip). The spline backward
+    takes the direction's input, which here is x itself."""
+
+    @staticmethod
+    def forward(ctx, made, bins, bound, x, context, *params):
+        from .spline import rqs_fwd
+
+        o, saved = _made_fwd(made, x, context)
+        y, ldj = rqs_fwd(o, x, bins, bound)
+        ctx.made, ctx.saved, ctx.bins, ctx.bound = made, saved, bins, bound
+        ctx.save_for_backward(x, o)
+        return y, ldj
+
+    @staticmethod
+    def backward(ctx, gy, gldj):
+        from .spline import rqs_bwd
+
+        x, o = ctx.saved_tensors
+        if gy is None:
+            gy = torch.zeros_like(x)
+        gl = gldj if gldj is not None else torch.zeros(x.shape[0], device=x.device)
+        dout, gx = rqs_bwd(o, x, gy.float().contiguous(), gl.float().contiguous(), ctx.bins,
+                           ctx.bound)
+        need = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
+        dx, dctx, grads = _made_bwd(ctx.made, ctx.saved, dout, gx, need)
+        if not need:
+            dx = None
+        ctx.saved = None
+        return (None, None, None, dx, dctx, *grads)
+
+
+def rqs_autoregressive(layer, x, context=None):
+    """(y, ldj) of a MADE-conditioned spline layer's one-pass direction through the fused path."""
+    made = layer.made
+    has_ctx = made.ctx is not None and context is not None
+    return _RQSAutoregressiveFn.apply(made, layer.bins, layer.bound, x.contiguous(),
                                       context if has_ctx else None, *_params(made, has_ctx))

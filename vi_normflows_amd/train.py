@@ -104,8 +104,8 @@ def run_flow_vi(cfg, out, info, logger):
     from .viz.plots import plot_density_and_samples, plot_loss
 
     dev = _device(cfg, info)
-    # spline-flow (flow=nsf), Sylvester (flow=sylvester) and neural autoregressive (flow=naf)
-    # options, passed through only when set
+    # spline-flow (flow=nsf coupling, flow=nsf-ar autoregressive), Sylvester (flow=sylvester) and
+    # neural autoregressive (flow=naf) options, passed through only when set
     flow_kw = {k: cfg.extra[k] for k in ("bins", "bound", "householders", "basis", "units",
                                          "conditioner")
                if cfg.extra.get(k) is not None}
