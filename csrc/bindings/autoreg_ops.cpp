@@ -1,7 +1,8 @@
 // TORCH_LIBRARY fragment for the autoregressive degree sweeps: MAF sampling and the IAF inverse
 // (made_sweep.hip), the inverse of a MADE-conditioned DSF layer (dsf_sweep.hip) and the sequential
-// direction of a MADE-conditioned spline layer (rqs_sweep.hip) in one masked pass. Not
-// differentiable.
+// direction of a MADE-conditioned spline layer (rqs_sweep.hip) in one masked pass, and the adjoint
+// sweep all three share (sweep_adjoint.hip). The ops themselves are not differentiable; the
+// implicit gradient is assembled in ops/autoregressive.py.
 #include <torch/library.h>
 #include <ATen/ATen.h>
 
@@ -156,9 +157,82 @@ bool rqs_sweep_supported(int64_t D, int64_t H, int64_t L, int64_t K) {
   return rqs_sweep_rows(D, H, L, K) > 0;
 }
 
+// The adjoint of the degree sweeps (sweep_adjoint.hip): gx, d [B, D]; q, c [B, D, P]
+// coordinate-major; hidden [l] [B, H] the activations at the solution; weights the L hidden layers
+// then the output layer [P D, H] plane-major. Writes w [B, D], pbar [B, D, P] (may be c) and
+// a[l] [B, H].
+void sweep_adjoint(const at::Tensor& gx, const at::Tensor& d, const at::Tensor& q,
+                   const at::Tensor& c, at::TensorList hidden, at::TensorList weights,
+                   const at::Tensor& perm, const at::Tensor& ubeg, const at::Tensor& w,
+                   const at::Tensor& pbar, at::TensorList a) {
+  const char* op = "sweep_adjoint";
+  TORCH_CHECK(gx.is_cuda() && gx.dim() == 2, op, ": gx must be a GPU tensor [B, D]");
+  const int64_t L = (int64_t)weights.size() - 1;
+  TORCH_CHECK(L >= 1 && L <= NF_MADE_SWEEP_MAX_HIDDEN && (int64_t)hidden.size() == L &&
+                  (int64_t)a.size() == L,
+              op, ": need 1 .. ", NF_MADE_SWEEP_MAX_HIDDEN,
+              " hidden layers plus the output layer, one h and one a per hidden layer");
+  TORCH_CHECK(weights[0].dim() == 2 && q.dim() == 3, op,
+              ": a hidden weight must be a matrix and q [B, D, P]");
+  const int64_t B = gx.size(0), D = gx.size(1), H = weights[0].size(0), P = q.size(2);
+  TORCH_CHECK(B >= 1 && B < (int64_t(1) << 31) && D >= 1 && H >= 1 && D < (1 << 24) &&
+                  H < (1 << 24) && P >= 1 && P <= NF_SWEEP_ADJOINT_MAX_P,
+              op, ": bad sizes B = ", B, ", D = ", D, ", H = ", H, ", P = ", P);
+  TORCH_CHECK(nf_sweep_adjoint_rows((int)D, (int)H, (int)L, (int)P) > 0, op, ": (D, H, L, P) = (",
+              D, ", ", H, ", ", L, ", ", P,
+              ") exceeds the kernel's LDS budget (sweep_adjoint_supported)");
+  const auto dev = gx.device();
+  NfSweepAdjoint s{};
+  s.B = (int)B; s.D = (int)D; s.H = (int)H; s.L = (int)L; s.P = (int)P;
+  s.ldg = mat_stride(op, gx, "gx", B, D, dev);
+  s.gx = gx.data_ptr<float>();
+  s.ldd = mat_stride(op, d, "d", B, D, dev);
+  s.d = d.data_ptr<float>();
+  chk_vec(op, q, "q", B * D * P, at::kFloat, dev);
+  chk_vec(op, c, "c", B * D * P, at::kFloat, dev);
+  chk_vec(op, pbar, "pbar", B * D * P, at::kFloat, dev);
+  s.q = q.data_ptr<float>();
+  s.c = c.data_ptr<float>();
+  s.pbar = pbar.data_ptr<float>();
+  for (int64_t l = 0; l < L; ++l) {
+    s.ldw[l] = mat_stride(op, weights[l], "a hidden weight", H, l == 0 ? D : H, dev);
+    s.W[l] = weights[l].data_ptr<float>();
+    s.ldh[l] = mat_stride(op, hidden[l], "a hidden activation", B, H, dev);
+    s.h[l] = hidden[l].data_ptr<float>();
+    s.lda[l] = mat_stride(op, a[l], "a hidden cotangent", B, H, dev);
+    s.a[l] = a[l].data_ptr<float>();
+  }
+  s.ldo = mat_stride(op, weights[L], "the output weight", P * D, H, dev);
+  s.Wo = weights[L].data_ptr<float>();
+  chk_vec(op, perm, "perm", D, at::kInt, dev);
+  chk_vec(op, ubeg, "ubeg", L * (D + 2), at::kInt, dev);
+  s.perm = perm.data_ptr<int>();
+  s.ubeg = ubeg.data_ptr<int>();
+  s.ldwo = mat_stride(op, w, "w", B, D, dev);
+  s.w = w.data_ptr<float>();
+  nf_launch_sweep_adjoint(s, cur_stream());
+}
+
+// rows per block for (D, H, L, P); 0 when the shape does not fit or P is out of range
+int64_t sweep_adjoint_rows(int64_t D, int64_t H, int64_t L, int64_t P) {
+  if (D < 1 || H < 1 || L < 1 || D >= (1 << 24) || H >= (1 << 24) ||
+      L > NF_MADE_SWEEP_MAX_HIDDEN || P < 1 || P > NF_SWEEP_ADJOINT_MAX_P)
+    return 0;
+  return nf_sweep_adjoint_rows((int)D, (int)H, (int)L, (int)P);
+}
+
+bool sweep_adjoint_supported(int64_t D, int64_t H, int64_t L, int64_t P) {
+  return sweep_adjoint_rows(D, H, L, P) > 0;
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(vinf, m) {
+  m.def("sweep_adjoint(Tensor gx, Tensor d, Tensor q, Tensor c, Tensor[] hidden, "
+        "Tensor[] weights, Tensor perm, Tensor ubeg, Tensor(a!) w, Tensor(b!) pbar, "
+        "Tensor(c!)[] a) -> ()");
+  m.def("sweep_adjoint_rows(int D, int H, int L, int P) -> int", &sweep_adjoint_rows);
+  m.def("sweep_adjoint_supported(int D, int H, int L, int P) -> bool", &sweep_adjoint_supported);
   m.def("made_sweep(Tensor v, Tensor[] weights, Tensor[] biases, Tensor perm, Tensor ubeg, "
         "int kind, float param, Tensor? ctx_bias, Tensor(a!) x, Tensor(b!) ldj) -> ()");
   m.def("made_sweep_rows(int D, int H, int L) -> int", &made_sweep_rows);
@@ -177,4 +251,5 @@ TORCH_LIBRARY_IMPL(vinf, CUDA, m) {
   m.impl("made_sweep", &made_sweep);
   m.impl("dsf_sweep", &dsf_sweep);
   m.impl("rqs_sweep", &rqs_sweep);
+  m.impl("sweep_adjoint", &sweep_adjoint);
 }

@@ -411,3 +411,37 @@ void nf_launch_dsf_sweep(const NfMadeSweep& s, int U, hipStream_t stream);
 // rows per block for (D, H, L, K); 0 = the shape is not supported
 int nf_rqs_sweep_rows(int D, int H, int L, int K);
 void nf_launch_rqs_sweep(const NfMadeSweep& s, int K, float bound, hipStream_t stream);
+
+// sweep_adjoint.hip: the transpose of the degree sweeps' forward substitution, walking the degrees
+// downwards: given gx = xbar - lbar e [B, D], d = dtau/dx [B, D] and, per coordinate, q = dtau/dp
+// and c = lbar dlog d/dp [B, D, P] (coordinate-major: the P values of one coordinate are
+// contiguous), it solves for w [B, D] (the cotangent of v), pbar = q w + c [B, D, P] (may alias c)
+// and a[l] = hbar_l [h_l > 0] [B, H] (the cotangents of the hidden pre-activations). h[l] [B, H]
+// are the hidden activations at the solution (used only for > 0); W[l] / Wo are the unmasked fp32
+// weights of NfMadeSweep with Wo [P D, H] plane-major, 1 <= P <= NF_SWEEP_ADJOINT_MAX_P.
+#define NF_SWEEP_ADJOINT_MAX_P 96
+struct NfSweepAdjoint {
+  const float* W[NF_MADE_SWEEP_MAX_HIDDEN];
+  long ldw[NF_MADE_SWEEP_MAX_HIDDEN];
+  const float* h[NF_MADE_SWEEP_MAX_HIDDEN];
+  long ldh[NF_MADE_SWEEP_MAX_HIDDEN];
+  float* a[NF_MADE_SWEEP_MAX_HIDDEN];
+  long lda[NF_MADE_SWEEP_MAX_HIDDEN];
+  const float* Wo;
+  long ldo;
+  const int* perm;
+  const int* ubeg;
+  const float* gx;
+  long ldg;
+  const float* d;
+  long ldd;
+  const float* q;     // [B, D, P] contiguous
+  const float* c;     // [B, D, P] contiguous
+  float* pbar;        // [B, D, P] contiguous
+  float* w;
+  long ldwo;
+  int B, D, H, L, P;
+};
+// rows per block for (D, H, L, P); 0 = the shape is not supported
+int nf_sweep_adjoint_rows(int D, int H, int L, int P);
+void nf_launch_sweep_adjoint(const NfSweepAdjoint& s, hipStream_t stream);

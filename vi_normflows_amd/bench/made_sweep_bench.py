@@ -8,13 +8,17 @@ passes and root solves that ``DSFAutoregressive.inverse`` runs when the sweep do
 
     python -m vi_normflows_amd.bench.made_sweep_bench [--flow maf|dsf|rqs] [--units 8] [--bins 8]
         [--batch 4096] [--d 256] [--hidden 512] [--layers 1] [--reps 20] [--baseline]
-        [--baseline-reps 3] [--density N]
+        [--baseline-reps 3] [--density N] [--backward]
 
 After a warm-up, the median of ``--reps`` HIP-event timings of the sweep; with ``--baseline`` the
 loop takes turns with it for ``--baseline-reps`` reps (it is D MADE passes: keep that small).
 ``--density N`` adds the end-to-end time of ``MAFDensity(MAFConfig()).sample(N)`` (config 5's
-64-layer model, sweep path only). One JSON line. Needs a GPU and the native library: there is no
-fallback.
+64-layer model, sweep path only). ``--backward`` times the implicit gradient instead
+(csrc/kernels/sweep_adjoint.hip): the adjoint sweep alone next to the forward sweep, the fp32
+pieces of the backward (masked pass, element derivatives, weight-gradient products) and the whole
+forward + backward of the layer with ``implicit_grad=True``; with ``--baseline`` (maf only) the
+differentiable D-pass loop under autograd takes turns with it. One JSON line. Needs a GPU and the
+native library: there is no fallback.
 """
 from __future__ import annotations
 
@@ -66,6 +70,65 @@ def sequential_rqs_inverse(flow, y):
     return z, -ldj
 
 
+def backward_record(flow, u, spec, run, reps, baseline_reps):
+    """Timings of the implicit gradient of one layer (see the module docstring)."""
+    from ..ops import autoregressive as ar
+
+    made = flow.made
+    W = [l.weight.detach() for l in made.layers]
+    b = [l.bias.detach() for l in made.layers]
+    plan = ar._plan_of(made)
+    P = ar._spec_planes(spec)
+    masks = plan.masks(P, u.device, u.dtype)
+    lbar = torch.ones(u.shape[0], device=u.device)
+    with torch.no_grad():
+        x, _ = run(u)
+        p, hidden = ar._masked_pass(x, W, b, masks, None)
+        le, d, q, c = ar._element_derivatives(spec, x, p, lbar)
+        gx = torch.ones_like(x) - le
+        w, pbar, a = ar.sweep_adjoint(gx, d, q, c, hidden, W, made.order, plan=plan)
+        pbar_pm = pbar.transpose(1, 2).reshape(u.shape[0], -1)
+
+        def wgrads():
+            for l in range(len(W)):
+                ar._wgrad(a[l] if l < len(W) - 1 else pbar_pm, x if l == 0 else hidden[l - 1],
+                          masks[l])
+
+        us = alternate({
+            "forward_sweep": lambda: run(u),
+            "adjoint_sweep": lambda: ar.sweep_adjoint(gx, d, q, c, hidden, W, made.order,
+                                                      plan=plan),
+            "masked_pass_fp32": lambda: ar._masked_pass(x, W, b, masks, None),
+            "element_derivatives": lambda: ar._element_derivatives(spec, x, p, lbar),
+            "weight_gradients_fp32": wgrads}, reps)
+    rec = {"us": {k: round(v, 1) for k, v in us.items()},
+           "adjoint_over_forward": round(us["adjoint_sweep"] / us["forward_sweep"], 2),
+           "adjoint_rows_per_block": ar.adjoint_kernel_rows(
+               made.dim, W[0].shape[0], len(W) - 1, P)}
+    ug = u.clone().requires_grad_()
+
+    def step(flag):
+        def f():
+            flow.implicit_grad = flag
+            flow.zero_grad(set_to_none=True)
+            ug.grad = None
+            x, l = run(ug)
+            (x.sum() + l.sum()).backward()
+        return f
+
+    n0 = ar.sweep_adjoint_launches()
+    rec["us"]["forward_backward_implicit"] = round(alternate({"i": step(True)}, reps)["i"], 1)
+    assert ar.sweep_adjoint_launches() > n0, "the implicit path did not run"
+    if baseline_reps:
+        ab = alternate({"implicit": step(True), "loop_autograd": step(False)}, baseline_reps,
+                       warmup=1)
+        rec["us_ab"] = {k: round(v, 1) for k, v in ab.items()}
+        rec["baseline_reps"] = baseline_reps
+        rec["speedup_vs_loop_autograd"] = round(ab["loop_autograd"] / ab["implicit"], 2)
+    flow.implicit_grad = False
+    return rec
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -80,6 +143,8 @@ def main(argv=None):
     ap.add_argument("--baseline", action="store_true")
     ap.add_argument("--baseline-reps", type=int, default=3)
     ap.add_argument("--density", type=int, default=0)
+    ap.add_argument("--backward", action="store_true",
+                    help="time the implicit gradient (sweep_adjoint.hip) instead")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("made_sweep_bench: needs a GPU (no CPU fallback)")
@@ -117,6 +182,18 @@ def main(argv=None):
     run = flow.inverse if dsf or rqs else flow
     sequential = (sequential_rqs_inverse if rqs else sequential_dsf_inverse if dsf
                   else sequential_sample)
+    if a.backward:
+        if a.baseline and (dsf or rqs):
+            raise SystemExit("made_sweep_bench: --backward --baseline needs --flow maf (the other "
+                             "layers have no differentiable loop)")
+        spec = (("rqs", a.bins, float(flow.bound)) if rqs else ("dsf", a.units) if dsf
+                else ("made", "maf_sample", float(flow.bound), 1.0, 1.0))
+        rec["bench"] = "sweep_adjoint"
+        rec["flow"] = a.flow
+        rec.update(backward_record(flow, u, spec, run, a.reps,
+                                   a.baseline_reps if a.baseline else 0))
+        print(json.dumps(rec), flush=True)
+        return
     with torch.no_grad():
         assert ar.dispatch(flow, u, None), "shape outside the sweep kernel's limits"
         fns = {"sweep": lambda: run(u)}

@@ -18,7 +18,10 @@ coordinates. Because the hidden degrees are sorted it is still one masked pass, 
 substitution in degree order: ``ops.autoregressive`` (``csrc/kernels/made_sweep.hip``) runs it for
 fp32 GPU tensors when nothing needs a graph. Otherwise - CPU tensors, grad mode on with an input
 or parameter that requires grad, a non-ReLU MADE, a shape outside the kernel's LDS budget - it is
-a loop of D full MADE passes.
+a loop of D full MADE passes. With ``implicit_grad=True`` a call that needs a graph takes the sweep
+too (on the CPU its torch composite, in any dtype) and backpropagates through it with the implicit
+gradient of ``ops.autoregressive``: one adjoint sweep instead of D graphs; outside the kernels'
+limits it keeps the loop.
 """
 from __future__ import annotations
 
@@ -128,11 +131,12 @@ class IAF(Flow):
 
     def __init__(self, dim: int, hidden: int, n_hidden: int = 1, context_dim: int = 0,
                  mode: str = "gated", gate_bias: float = 1.0, reverse: bool = False,
-                 scale_bound: float = 1.0):
+                 scale_bound: float = 1.0, implicit_grad: bool = False):
         super().__init__()
         order = torch.arange(dim, 0, -1) if reverse else None
         self.made = MADE(dim, hidden, n_hidden, 2, context_dim, order)
         self.mode, self.gate_bias, self.scale = mode, gate_bias, scale_bound
+        self.implicit_grad = bool(implicit_grad)
         self.uses_context = context_dim > 0
 
     def forward(self, z, context=None):
@@ -160,10 +164,15 @@ class IAF(Flow):
 
         if autoregressive.dispatch(self, y, context):
             return autoregressive.made_sweep_flow(self, y, context)
+        if self.implicit_grad and autoregressive.needs_graph(self, y, context) \
+                and autoregressive.grad_supported(self.made, y, context):
+            return autoregressive.made_sweep_flow_grad(self, y, context)
         z = torch.zeros_like(y)
         for i in self._order_idx():
             out = self.made(z, context)
             m, s = out[:, 0, i], out[:, 1, i]
+            if torch.is_grad_enabled():
+                z = z.clone()   # the MADE pass above saved z: autograd forbids writing into it
             if self.mode == "gated":
                 sig = torch.sigmoid(s + self.gate_bias)
                 z[:, i] = (y[:, i] - (1 - sig) * m) / sig
@@ -182,11 +191,12 @@ class MAF(Flow):
     invertible = True
 
     def __init__(self, dim: int, hidden: int, n_hidden: int = 1, context_dim: int = 0,
-                 reverse: bool = False, alpha_bound: float = 5.0):
+                 reverse: bool = False, alpha_bound: float = 5.0, implicit_grad: bool = False):
         super().__init__()
         order = torch.arange(dim, 0, -1) if reverse else None
         self.made = MADE(dim, hidden, n_hidden, 2, context_dim, order)
         self.bound = alpha_bound
+        self.implicit_grad = bool(implicit_grad)
         self.uses_context = context_dim > 0
 
     def _mu_alpha(self, x, context):
@@ -209,6 +219,9 @@ class MAF(Flow):
 
         if autoregressive.dispatch(self, u, context):
             return autoregressive.made_sweep_flow(self, u, context)
+        if self.implicit_grad and autoregressive.needs_graph(self, u, context) \
+                and autoregressive.grad_supported(self.made, u, context):
+            return autoregressive.made_sweep_flow_grad(self, u, context)
         x = torch.zeros_like(u)
         for i in torch.argsort(self.made.order).tolist():
             mu, alpha = self._mu_alpha(x, context)

@@ -76,8 +76,9 @@ class DSFAutoregressive(Flow):
     invertible = True
 
     def __init__(self, dim: int, units: int = 8, hidden: int = 64, n_hidden: int = 1,
-                 context_dim: int = 0, reverse: bool = False):
+                 context_dim: int = 0, reverse: bool = False, implicit_grad: bool = False):
         super().__init__()
+        self.implicit_grad = bool(implicit_grad)
         self.dim, self.units = dim, _check_units("DSFAutoregressive", units)
         order = torch.arange(dim, 0, -1) if reverse else None
         self.made = MADE(dim, hidden, n_hidden, 3 * self.units, context_dim, order)
@@ -94,11 +95,28 @@ class DSFAutoregressive(Flow):
         y, ldj = dsf_transform(self._params(z, context), z, self.units)
         return y.to(z.dtype), ldj
 
-    @torch.no_grad()
     def inverse(self, y, context=None):
-        """Inverse ``(z, -ldj)``, for sampling and checks: it runs without a graph and is not
-        differentiated. fp32 GPU tensors with a supported MADE (ReLU, 1 .. 4 hidden layers, a
-        bias on every layer, a shape inside the kernel's LDS budget) take the degree sweep of
+        """Inverse ``(z, -ldj)``. By default it runs without a graph and is not differentiated;
+        with ``implicit_grad=True`` a call that needs a graph takes the degree sweep (on the CPU
+        its torch composite, in any dtype) with the implicit gradient of ``ops.autoregressive``,
+        and raises where the sweep is not supported: the layer has no other differentiable
+        inverse."""
+        from ..ops import autoregressive as ar
+
+        if self.implicit_grad and ar.needs_graph(self, y, context):
+            if not ar.grad_supported(self.made, y, context, 3 * self.units):
+                raise RuntimeError(
+                    "DSFAutoregressive.inverse: implicit_grad needs a ReLU MADE with 1 .. 4 hidden "
+                    "layers and, on the GPU, fp32 tensors and a shape inside the sweep kernels' "
+                    f"LDS budget; got {tuple(y.shape)} {y.dtype} with hidden "
+                    f"{self.made.layers[0].weight.shape[0]} x {len(self.made.layers) - 1}")
+            return ar.dsf_sweep_flow_grad(self, y, context)
+        return self._inverse_no_grad(y, context)
+
+    @torch.no_grad()
+    def _inverse_no_grad(self, y, context=None):
+        """``(z, -ldj)`` without a graph, for sampling and checks. fp32 GPU tensors with a
+        supported MADE (ReLU, 1 .. 4 hidden layers, a bias on every layer, a shape inside the kernel's LDS budget) take the degree sweep of
         ``ops.autoregressive``: one masked pass with the root solve as the per-coordinate
         transform, ldj from the same kernel. Every other call (CPU, fp64, other shapes) runs
         the sequential loop: D MADE passes, each followed by the root solve of one coordinate,
@@ -123,12 +141,16 @@ class NeuralAutoregressiveFlow(Flow):
     invertible = True
 
     def __init__(self, dim: int, n_layers: int = 4, units: int = 8, hidden: int = 64,
-                 n_hidden: int = 1, conditioner: str = "made", context_dim: int = 0):
+                 n_hidden: int = 1, conditioner: str = "made", context_dim: int = 0,
+                 implicit_grad: bool = False):
         super().__init__()
+        if implicit_grad and conditioner != "made":
+            raise ValueError("NeuralAutoregressiveFlow: implicit_grad needs conditioner='made'")
         layers = []
         if conditioner == "made":
             for i in range(n_layers):
-                layers.append(DSFAutoregressive(dim, units, hidden, n_hidden, context_dim))
+                layers.append(DSFAutoregressive(dim, units, hidden, n_hidden, context_dim,
+                                                implicit_grad=implicit_grad))
                 if i < n_layers - 1:
                     layers.append(Reverse())
         elif conditioner == "coupling":

@@ -116,8 +116,9 @@ class RQSAutoregressive(Flow):
 
     def __init__(self, dim: int, bins: int = 8, bound: float = 3.0, hidden: int = 64,
                  n_hidden: int = 1, context_dim: int = 0, reverse: bool = False,
-                 density: bool = False):
+                 density: bool = False, implicit_grad: bool = False):
         super().__init__()
+        self.implicit_grad = bool(implicit_grad)
         if not 2 <= bins <= 32:
             raise ValueError(f"RQSAutoregressive: need 2 <= bins <= 32, got {bins}")
         if not bound > 0:
@@ -140,11 +141,28 @@ class RQSAutoregressive(Flow):
         y, ldj = rqs_transform(self._params(x, context), x, self.bins, self.bound)
         return y.to(x.dtype), ldj
 
-    @torch.no_grad()
     def _sequential(self, y, context=None):
-        """``(z, -ldj_T(z))`` with ``T(z) = y``, for sampling and checks: it runs without a graph
-        and is not differentiated. fp32 GPU tensors with a supported MADE (ReLU, 1 .. 4 hidden
-        layers, a bias on every layer, a shape inside the kernel's LDS budget) take the degree
+        """``(z, -ldj_T(z))`` with ``T(z) = y``. By default it runs without a graph and is not
+        differentiated; with ``implicit_grad=True`` a call that needs a graph takes the degree
+        sweep (on the CPU its torch composite, in any dtype) with the implicit gradient of
+        ``ops.autoregressive``, and raises where the sweep is not supported: the layer has no
+        other differentiable solve."""
+        from ..ops import autoregressive as ar
+
+        if self.implicit_grad and ar.needs_graph(self, y, context):
+            if not ar.grad_supported(self.made, y, context, 3 * self.bins - 1):
+                raise RuntimeError(
+                    "RQSAutoregressive: implicit_grad needs a ReLU MADE with 1 .. 4 hidden layers "
+                    "and, on the GPU, fp32 tensors and a shape inside the sweep kernels' LDS "
+                    f"budget; got {tuple(y.shape)} {y.dtype} with hidden "
+                    f"{self.made.layers[0].weight.shape[0]} x {len(self.made.layers) - 1}")
+            return ar.rqs_sweep_flow_grad(self, y, context)
+        return self._sequential_no_grad(y, context)
+
+    @torch.no_grad()
+    def _sequential_no_grad(self, y, context=None):
+        """``(z, -ldj_T(z))`` with ``T(z) = y`` without a graph, for sampling and checks. fp32
+        GPU tensors with a supported MADE (ReLU, 1 .. 4 hidden layers, a bias on every layer, a shape inside the kernel's LDS budget) take the degree
         sweep of ``ops.autoregressive``: one masked pass with the closed-form spline inverse as
         the per-coordinate transform, ldj from the same kernel. Every other call (CPU, fp64,
         other shapes) runs the sequential loop: D MADE passes, each followed by the spline
@@ -180,12 +198,12 @@ class MaskedSplineFlow(Flow):
 
     def __init__(self, dim: int, n_layers: int = 4, bins: int = 8, bound: float = 3.0,
                  hidden: int = 64, n_hidden: int = 1, context_dim: int = 0,
-                 density: bool = False):
+                 density: bool = False, implicit_grad: bool = False):
         super().__init__()
         layers = []
         for i in range(n_layers):
             layers.append(RQSAutoregressive(dim, bins, bound, hidden, n_hidden, context_dim,
-                                            density=density))
+                                            density=density, implicit_grad=implicit_grad))
             if i < n_layers - 1:
                 layers.append(Reverse())
         self.density = bool(density)

@@ -54,7 +54,8 @@ def build_flow(kind: str, dim: int, K: int, **kw):
 
         return MaskedSplineFlow(dim, n_layers=K, bins=kw.get("bins", 8),
                                 bound=kw.get("bound", 3.0), hidden=kw.get("hidden", 64),
-                                density=kw.get("density", False))
+                                density=kw.get("density", False),
+                                implicit_grad=kw.get("implicit_grad", False))
     if kind == "sylvester":
         from ..flows.sylvester import SylvesterStack
 
@@ -65,14 +66,16 @@ def build_flow(kind: str, dim: int, K: int, **kw):
 
         return NeuralAutoregressiveFlow(dim, n_layers=K, units=kw.get("units", 8),
                                         hidden=kw.get("hidden", 64),
-                                        conditioner=kw.get("conditioner", "made"))
-    if kind == "iaf":
+                                        conditioner=kw.get("conditioner", "made"),
+                                        implicit_grad=kw.get("implicit_grad", False))
+    if kind in ("iaf", "maf"):
         from ..flows.base import Reverse
-        from ..flows.made import IAF
+        from ..flows.made import IAF, MAF
 
         layers = []
         for i in range(K):
-            layers.append(IAF(dim, kw.get("hidden", 64), 1))
+            layers.append((IAF if kind == "iaf" else MAF)(
+                dim, kw.get("hidden", 64), 1, implicit_grad=kw.get("implicit_grad", False)))
             if i < K - 1:
                 layers.append(Reverse())
         return FlowSequence(layers)

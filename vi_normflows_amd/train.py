@@ -105,9 +105,10 @@ def run_flow_vi(cfg, out, info, logger):
 
     dev = _device(cfg, info)
     # spline-flow (flow=nsf coupling, flow=nsf-ar autoregressive), Sylvester (flow=sylvester) and
-    # neural autoregressive (flow=naf) options, passed through only when set
+    # neural autoregressive (flow=naf) options, and the implicit gradient of the degree sweeps
+    # (extra.implicit_grad, for flow=maf / iaf / naf / nsf-ar), passed through only when set
     flow_kw = {k: cfg.extra[k] for k in ("bins", "bound", "householders", "basis", "units",
-                                         "conditioner")
+                                         "conditioner", "implicit_grad")
                if cfg.extra.get(k) is not None}
     r = fit_flow_vi(cfg.target, cfg.flow, cfg.K, cfg.iters, cfg.lr, cfg.batch, cfg.optimizer,
                     cfg.schedule, device=dev, seed=rank_seed(cfg.seed, info.rank),
