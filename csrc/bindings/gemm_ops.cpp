@@ -486,6 +486,16 @@ void gemm_nn_cpl(const at::Tensor& dy, const at::Tensor& W, const at::Tensor& G,
   TORCH_CHECK(s_hat.scalar_type() == at::kBFloat16 && s_hat.size(1) >= Dh, "s_hat: bf16 [M, >= Dh]");
   TORCH_CHECK(dst.scalar_type() == at::kBFloat16 && dst.size(1) >= 2 * Dh && dst.size(1) <= Dh + N,
               "dst: bf16 [M, 2 Dh .. Dh + N]");
+  // the staged epilogue's row accesses (staged_ok in gemm_tile.h; the launcher has no other path)
+  auto al = [](const at::Tensor& t, uintptr_t a) {
+    return reinterpret_cast<uintptr_t>(t.data_ptr()) % a == 0;
+  };
+  TORCH_CHECK(Dh % 4 == 0 && N % 4 == 0 && ld2(G) % 4 == 0 && ld2(x) % 4 == 0 &&
+                  ld2(gx) % 4 == 0 && ld2(dst) % 4 == 0 && ld2(s_hat) % 4 == 0,
+              "gemm_nn_cpl: Dh, N and every leading dimension must be multiples of 4");
+  TORCH_CHECK(al(G, g_bf16 ? 8 : 16) && al(x, x_bf16 ? 8 : 16) && al(gx, gx_bf16 ? 8 : 16) &&
+                  al(dst, 8) && al(s_hat, 8),
+              "gemm_nn_cpl: G / x / gx must be 16-B aligned (8-B as bf16), dst / s_hat 8-B aligned");
   nf_launch_gemm256_nn_cpl(dy.data_ptr(), ld2(dy), use_wt ? Wt->data_ptr() : W.data_ptr(),
                            use_wt ? ld2(*Wt) : ld2(W), (const float*)G.data_ptr(),
                            ld2(G), M, N, K, s_hat.data_ptr(), ld2(s_hat), (const float*)x.data_ptr(),
@@ -529,6 +539,7 @@ void maf_gemm_fwd(const at::Tensor& h, const c10::optional<at::Tensor>& hs, cons
               "maf_gemm_fwd: u may be omitted only with a ubf output (a bf16 state)");
   const int M = h.size(0), K = h.size(1), D = x.size(1);
   TORCH_CHECK(W.size(0) == 2 * D && W.size(1) == K, "W must be [2D, K]");
+  TORCH_CHECK(K % (f8 ? 128 : 32) == 0, "maf_gemm_fwd: K must be a multiple of 32 (e4m3: 128)");
   TORCH_CHECK(D % 128 == 0 && x.size(0) == M && (!has_u || (u->size(0) == M && u->size(1) == D)) &&
                   s_out.size(0) == M && s_out.size(1) == D, "maf_gemm_fwd shapes (D % 128 == 0)");
   chk_ranges(krange, D / 128, "krange");
@@ -684,6 +695,7 @@ void maf_gemm_bwd(const at::Tensor& dy, const at::Tensor& Wt, const at::Tensor& 
   chk_mat(gx, "gx", at::kFloat);
   const int M = dy.size(0), K = dy.size(1), D = Wt.size(0);
   TORCH_CHECK(Wt.size(1) == K && K % 32 == 0 && D % 8 == 0, "Wt must be [D, K], K % 32 == 0");
+  TORCH_CHECK(!f8 || K % 128 == 0, "maf_gemm_bwd: e4m3 operands need K % 128 == 0");
   for (const at::Tensor* t : {&G, &s_raw, &u, &gx})
     TORCH_CHECK(t->size(0) == M && t->size(1) == D, "G / s_raw / u / gx: [M, D]");
   TORCH_CHECK(!has_dst || (dst_opt->size(0) == M && dst_opt->size(1) == 2 * D),

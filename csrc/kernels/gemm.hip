@@ -610,10 +610,13 @@ void nf_launch_gemm_tn_masked(const void* dy, long lddy, const void* x, long ldx
 // profiles/r1_wgrad_group_256.jsonl); it has no masked-tile skipping, so MADE groups stay on 128.
 static bool group_use_256(int nprob, const NfTnProblem* pr) {
   if (g_tile_mode < 0) use_256(1, 1, 1);
+  // skip flags are per 128x128 tile: the 256x256 kernel would index them by its own tile ids
+  for (int p = 0; p < nprob; ++p)
+    if (pr[p].skip) return false;
   if (g_tile_mode == 3) return true;
   if (g_tile_mode != 0) return false;
   for (int p = 0; p < nprob; ++p)
-    if (pr[p].skip || pr[p].K < 8192) return false;
+    if (pr[p].K < 8192) return false;
   return true;
 }
 
