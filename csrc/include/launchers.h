@@ -445,3 +445,28 @@ struct NfSweepAdjoint {
 // rows per block for (D, H, L, P); 0 = the shape is not supported
 int nf_sweep_adjoint_rows(int D, int H, int L, int P);
 void nf_launch_sweep_adjoint(const NfSweepAdjoint& s, hipStream_t stream);
+
+// lu_solve.hip: x = (P L U)^-1 (y - b) per batch row and its transpose, against a packed factor
+// A [D, D] (mode 0 = LU: strict lower triangle L with an implied unit diagonal, upper triangle U
+// with its diagonal; mode 1 = LOWER: the lower triangle with its diagonal is the one factor, the
+// strict upper triangle is never read), W = (L U)[perm, :].
+//   transpose 0: s[:, perm[i]] = y[:, i] - bias[i]; L z = s; U x = z; x stored.
+//   transpose 1: U^T q = y; L^T g = q; g[:, perm] stored (W^-T y; bias unused).
+// M is the EQUATION-major orientation of the factor, M[k][i] = the coefficient of unknown k in
+// equation i: A^T for transpose 0, A itself for transpose 1. fp32, unit inner strides with row
+// strides in elements; perm (int32 device array, clamped to [0, D)) and bias may be null.
+struct NfLuSolve {
+  const float* M;
+  long ldm;
+  const float* y;
+  long ldy;
+  const int* perm;
+  const float* bias;
+  float* x;
+  long ldx;
+  int B, D, mode, transpose;
+};
+// rows per block the launcher picks for D: the largest tile whose LDS state fits the budget it
+// requests; 0 = D is not supported (1 <= D <= 2048 is)
+int nf_lu_solve_rows(int D);
+void nf_launch_lu_solve(const NfLuSolve& s, hipStream_t stream);

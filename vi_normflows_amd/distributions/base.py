@@ -77,6 +77,63 @@ class DiagNormal(Distribution):
         return 0.5 * self.dim * (1.0 + LOG2PI) + 0.5 * self.logvar.sum()
 
 
+class FullRankNormal(Distribution):
+    """N(mean, L L^T) with a learnable lower-triangular scale: ``lower`` holds the strict lower
+    triangle of ``L`` and ``diag(L) = 1e-3 + softplus(raw_diag)`` (the parametrisation of
+    ``flows.linear``); it starts at N(0, I). The full-rank counterpart of ``DiagNormal``.
+    ``log_prob`` whitens with one triangular solve (``ops.linear_flow.lu_solve``,
+    ``mode="lower"``)."""
+
+    def __init__(self, dim: int, mean=None, lower=None, raw_diag=None):
+        super().__init__()
+        from ..flows.linear import RAW_DIAG_ONE
+
+        self.dim = dim
+        self.mean = nn.Parameter(torch.zeros(dim) if mean is None else
+                                 torch.as_tensor(mean, dtype=torch.float32).clone())
+        self.lower = nn.Parameter(torch.zeros(dim, dim) if lower is None else
+                                  torch.as_tensor(lower, dtype=torch.float32).clone())
+        self.raw_diag = nn.Parameter(torch.full((dim,), RAW_DIAG_ONE) if raw_diag is None else
+                                     torch.as_tensor(raw_diag, dtype=torch.float32).clone())
+
+    def diag(self):
+        from ..flows.linear import positive_diag
+
+        return positive_diag(self.raw_diag)
+
+    @property
+    def scale_tril(self):
+        return torch.tril(self.lower, -1) + torch.diag(self.diag())
+
+    @property
+    def covariance(self):
+        L = self.scale_tril
+        return L @ L.T
+
+    def entropy(self):
+        return 0.5 * self.dim * (1.0 + LOG2PI) + torch.log(self.diag()).sum()
+
+    def _log_density(self, eps):
+        return (-0.5 * self.dim * LOG2PI - torch.log(self.diag()).sum()
+                - 0.5 * (eps * eps).sum(1))
+
+    def log_prob(self, z):
+        from ..ops.linear_flow import lu_solve
+
+        eps = lu_solve(z, self.scale_tril, None, self.mean, mode="lower", impl="auto")
+        return self._log_density(eps)
+
+    def rsample_with_log_prob(self, n, generator=None):
+        from ..ops.linear import linear
+
+        eps = torch.randn(n, self.dim, device=self.mean.device, dtype=self.mean.dtype,
+                          generator=generator)
+        return linear(eps, self.scale_tril, self.mean), self._log_density(eps)
+
+    def rsample(self, n, generator=None):
+        return self.rsample_with_log_prob(n, generator)[0]
+
+
 class MVN(Distribution):
     """Full-covariance Gaussian (fixed)."""
 

@@ -1,9 +1,10 @@
 """Normalizing-flow layers: planar, radial, diagonal affine, RealNVP coupling, MADE/IAF/MAF,
 rational-quadratic spline (coupling and autoregressive), Sylvester, neural autoregressive (deep
-sigmoidal)."""
+sigmoidal), LU-parameterised linear and triangular affine."""
 from .affine import DiagAffine
 from .base import Flow, FlowDistribution, FlowSequence, Permute, Reverse
 from .coupling import AffineCoupling, RealNVP, coupling_transform
+from .linear import LULinear, TriangularAffine
 from .made import IAF, MADE, MAF, MaskedLinear, made_degrees, made_masks
 from .naf import DSFAutoregressive, DSFCoupling, NeuralAutoregressiveFlow
 from .planar import (AmortizedPlanar, Planar, PlanarStack, get_uhat, m, planar_flow,
@@ -25,5 +26,5 @@ __all__ = [
     "SylvesterStack", "AmortizedSylvester",
     "DSFCoupling", "DSFAutoregressive", "NeuralAutoregressiveFlow",
     "planar_stack_inverse", "planar_stack_inverse_reference", "radial_stack_inverse",
-    "radial_stack_inverse_reference",
+    "radial_stack_inverse_reference", "LULinear", "TriangularAffine",
 ]

@@ -73,30 +73,46 @@ class RQSCoupling(Flow):
 
 
 class NeuralSplineFlow(Flow):
-    """Stack of alternating-parity spline couplings."""
+    """Stack of alternating-parity spline couplings. ``linear="lu"`` puts an ``LULinear``
+    (seeded by its position) before every coupling, as in neural spline flows; the default
+    ``None`` has the couplings alone."""
 
     invertible = True
 
     def __init__(self, dim: int, n_layers: int = 4, bins: int = 8, bound: float = 3.0,
-                 hidden: int = 256, n_hidden: int = 2, context_dim: int = 0):
+                 hidden: int = 256, n_hidden: int = 2, context_dim: int = 0, linear=None):
         super().__init__()
+        if linear not in (None, "lu"):
+            raise ValueError(f"NeuralSplineFlow: linear must be None or 'lu', got {linear!r}")
         self.layers = nn.ModuleList(
             RQSCoupling(dim, bins, bound, hidden, n_hidden, parity=i % 2, context_dim=context_dim)
             for i in range(n_layers))
+        if linear == "lu":
+            from .linear import LULinear
+
+            self.linears = nn.ModuleList(LULinear(dim, seed=i) for i in range(n_layers))
+        else:
+            self.linears = None
         self.uses_context = context_dim > 0
 
     def forward(self, x, context=None):
         ldj = torch.zeros(x.shape[0], device=x.device)
-        for f in self.layers:
+        for i, f in enumerate(self.layers):
+            if self.linears is not None:
+                x, l = self.linears[i](x)
+                ldj = ldj + l
             x, l = f(x, context)
             ldj = ldj + l
         return x, ldj
 
     def inverse(self, y, context=None):
         ldj = torch.zeros(y.shape[0], device=y.device)
-        for f in reversed(self.layers):
-            y, l = f.inverse(y, context)
+        for i in reversed(range(len(self.layers))):
+            y, l = self.layers[i].inverse(y, context)
             ldj = ldj + l
+            if self.linears is not None:
+                y, l = self.linears[i].inverse(y)
+                ldj = ldj + l
         return y, ldj
 
 

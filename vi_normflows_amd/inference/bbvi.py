@@ -62,6 +62,58 @@ def black_box_vi(logprob, D: int, num_samples: int = 1000, iters: int = 1000, lr
     return BBVIResult(mean.detach(), log_std.detach(), trace)
 
 
+@dataclass
+class FullRankBBVIResult:
+    mean: torch.Tensor
+    scale_tril: torch.Tensor
+    trace: list
+
+    @property
+    def cov(self):
+        return self.scale_tril @ self.scale_tril.T
+
+
+def black_box_vi_full_rank(logprob, D: int, num_samples: int = 1000, iters: int = 1000,
+                           lr: float = 0.1, seed: int = 0, init_mean=None, init_log_std=None,
+                           log_every: int = 100, callback=None) -> FullRankBBVIResult:
+    """Maximise E_q[log p(w)] + H[q] for the full-rank q = N(mean, L L^T) (full-rank ADVI,
+    Kucukelbir et al. 2017): ``L`` lower triangular with a free strict lower triangle and
+    ``diag(L) = 1e-3 + softplus(raw_diag)``, starting at ``diag(exp(init_log_std))``. Same
+    arguments and fp64 Adam loop as :func:`black_box_vi`; ``callback(t, lower, mean, scale_tril)``."""
+    from ..flows.linear import DIAG_FLOOR, positive_diag
+
+    g = torch.Generator().manual_seed(seed)
+    mean = torch.zeros(D, dtype=torch.float64) if init_mean is None else \
+        torch.as_tensor(init_mean, dtype=torch.float64).clone()
+    std0 = torch.ones(D, dtype=torch.float64) if init_log_std is None else \
+        torch.exp(torch.as_tensor(init_log_std, dtype=torch.float64))
+    raw_diag = torch.log(torch.expm1((std0 - DIAG_FLOOR).clamp_min(1e-6)))
+    lower = torch.zeros(D, D, dtype=torch.float64)
+    for p in (mean, lower, raw_diag):
+        p.requires_grad_(True)
+    opt = torch.optim.Adam([mean, lower, raw_diag], lr=lr)
+
+    def scale_tril():
+        return torch.tril(lower, -1) + torch.diag(positive_diag(raw_diag))
+
+    trace = []
+    for t in range(iters):
+        eps = torch.randn(num_samples, D, generator=g, dtype=torch.float64)
+        L = scale_tril()
+        w = eps @ L.T + mean
+        entropy = 0.5 * D * (1.0 + LOG2PI) + torch.log(torch.diagonal(L)).sum()
+        lower_bound = entropy + logprob(w).mean()
+        loss = -lower_bound
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        if t % log_every == 0 or t == iters - 1:
+            trace.append((t, float(lower_bound.detach())))
+            if callback:
+                callback(t, float(lower_bound), mean.detach(), L.detach())
+    return FullRankBBVIResult(mean.detach(), scale_tril().detach(), trace)
+
+
 def design(x: torch.Tensor) -> torch.Tensor:
     """[1, x] design matrix (statsmodels.add_constant)."""
     x = torch.as_tensor(x, dtype=torch.float64).reshape(-1)

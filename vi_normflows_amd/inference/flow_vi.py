@@ -48,7 +48,12 @@ def build_flow(kind: str, dim: int, K: int, **kw):
         from ..flows.spline import NeuralSplineFlow
 
         return NeuralSplineFlow(dim, n_layers=K, hidden=kw.get("hidden", 64),
-                                bins=kw.get("bins", 8), bound=kw.get("bound", 4.0))
+                                bins=kw.get("bins", 8), bound=kw.get("bound", 4.0),
+                                linear=kw.get("linear"))
+    if kind == "affine-full":      # the full-rank Gaussian family (K is not used)
+        from ..flows.linear import TriangularAffine
+
+        return TriangularAffine(dim)
     if kind == "nsf-ar":
         from ..flows.spline import MaskedSplineFlow
 

@@ -106,9 +106,10 @@ def run_flow_vi(cfg, out, info, logger):
     dev = _device(cfg, info)
     # spline-flow (flow=nsf coupling, flow=nsf-ar autoregressive), Sylvester (flow=sylvester) and
     # neural autoregressive (flow=naf) options, and the implicit gradient of the degree sweeps
-    # (extra.implicit_grad, for flow=maf / iaf / naf / nsf-ar), passed through only when set
+    # (extra.implicit_grad, for flow=maf / iaf / naf / nsf-ar) and the LU-linear layers of flow=nsf
+    # (extra.linear=lu), passed through only when set
     flow_kw = {k: cfg.extra[k] for k in ("bins", "bound", "householders", "basis", "units",
-                                         "conditioner", "implicit_grad")
+                                         "conditioner", "implicit_grad", "linear")
                if cfg.extra.get(k) is not None}
     r = fit_flow_vi(cfg.target, cfg.flow, cfg.K, cfg.iters, cfg.lr, cfg.batch, cfg.optimizer,
                     cfg.schedule, device=dev, seed=rank_seed(cfg.seed, info.rank),
