@@ -40,8 +40,11 @@ void chk_q(const at::Tensor& t, const char* n) {
 void chk_ranges(const at::Tensor& r, long ntiles, const char* n);
 
 // y = act(x W^T + b): x [M,K], W [N,K], b [N] (bf16), y [M,N] bf16
-void gemm_nt(const at::Tensor& x, const at::Tensor& W, const c10::optional<at::Tensor>& b,
-             const at::Tensor& y, int64_t relu, const c10::optional<at::Tensor>& mask) {
+// mask_lanes: write the mask in the 256x256 kernel's lane-private layout (gemm_tile.h); returns
+// NF_LANES_OK (0) when launched, else the reason nothing was launched (launchers.h)
+int64_t gemm_nt(const at::Tensor& x, const at::Tensor& W, const c10::optional<at::Tensor>& b,
+                const at::Tensor& y, int64_t relu, const c10::optional<at::Tensor>& mask,
+                bool mask_lanes) {
   chk_mat(x, "x", at::kBFloat16);
   chk_mat(W, "W", at::kBFloat16);
   chk_mat(y, "y", at::kBFloat16);
@@ -67,8 +70,16 @@ void gemm_nt(const at::Tensor& x, const at::Tensor& W, const c10::optional<at::T
     mp = mask->data_ptr();
     ldm = ld2(*mask);
   }
-  nf_launch_gemm_nt(x.data_ptr(), ld2(x), W.data_ptr(), ld2(W), bp, y.data_ptr(), ld2(y), M, N, K,
-                    (int)relu, cur_stream(), mp, ldm);
+  if (mask_lanes) {
+    TORCH_CHECK(mp, "mask_lanes needs a mask");
+    if (!mask->is_contiguous()) return NF_LANES_SHAPE;   // the layout covers the whole buffer
+  }
+  return nf_launch_gemm_nt(x.data_ptr(), ld2(x), W.data_ptr(), ld2(W), bp, y.data_ptr(), ld2(y), M,
+                           N, K, (int)relu, cur_stream(), mp, ldm, mask_lanes ? 1 : 0);
+}
+
+int64_t gemm_mask_lanes_route(int64_t M, int64_t N, int64_t K_fwd, int64_t K_bwd, bool bwd_wt) {
+  return nf_gemm_mask_lanes_route((int)M, (int)N, (int)K_fwd, (int)K_bwd, bwd_wt ? 1 : 0);
 }
 
 // y = x W^T: x [M,K], W [N,K] bf16, y [M,N] fp32 (the accumulator, unrounded)
@@ -127,9 +138,11 @@ void gemm_fp(const at::Tensor& A, bool a_kmajor, const at::Tensor& B, bool b_kma
 }
 
 // dx = dy W  [* 1(h > 0)]: dy [M,K], W [K,N] bf16; dx bf16 (mask) or fp32 (+= when accumulate)
-void gemm_nn(const at::Tensor& dy, const at::Tensor& W, const c10::optional<at::Tensor>& h,
-             const at::Tensor& dx, bool accumulate, const c10::optional<at::Tensor>& hbits,
-             const c10::optional<at::Tensor>& Wt) {
+// hbits_lanes: hbits is in the lane-private layout gemm_nt(mask_lanes=True) wrote; return value
+// as for gemm_nt
+int64_t gemm_nn(const at::Tensor& dy, const at::Tensor& W, const c10::optional<at::Tensor>& h,
+                const at::Tensor& dx, bool accumulate, const c10::optional<at::Tensor>& hbits,
+                const c10::optional<at::Tensor>& Wt, bool hbits_lanes) {
   chk_mat(dy, "dy", at::kBFloat16);
   chk_mat(W, "W", at::kBFloat16);
   const bool f32 = dx.scalar_type() == at::kFloat;
@@ -164,15 +177,18 @@ void gemm_nn(const at::Tensor& dy, const at::Tensor& W, const c10::optional<at::
     hp = hbits->data_ptr();
     ldh = ld2(*hbits);
     bits = 1;
+    if (hbits_lanes) {
+      if (!hbits->is_contiguous()) return NF_LANES_SHAPE;
+      bits = 2;
+    }
   }
+  TORCH_CHECK(!hbits_lanes || bits, "hbits_lanes needs hbits");
   TORCH_CHECK(!accumulate || f32, "accumulate needs an fp32 output");
-  if (use_wt) {
-    nf_launch_gemm256_nt_dgrad(dy.data_ptr(), ld2(dy), Wt->data_ptr(), ld2(*Wt), hp, ldh, bits,
-                               dx.data_ptr(), ld2(dx), M, N, K, cur_stream());
-    return;
-  }
-  nf_launch_gemm_nn(dy.data_ptr(), ld2(dy), W.data_ptr(), ld2(W), hp, ldh, dx.data_ptr(), ld2(dx),
-                    f32, accumulate, M, N, K, cur_stream(), bits);
+  if (use_wt)
+    return nf_launch_gemm256_nt_dgrad(dy.data_ptr(), ld2(dy), Wt->data_ptr(), ld2(*Wt), hp, ldh,
+                                      bits, dx.data_ptr(), ld2(dx), M, N, K, cur_stream());
+  return nf_launch_gemm_nn(dy.data_ptr(), ld2(dy), W.data_ptr(), ld2(W), hp, ldh, dx.data_ptr(),
+                           ld2(dx), f32, accumulate, M, N, K, cur_stream(), bits);
 }
 
 // batched bf16 transposes: desc = int64 [n, 5] device table of (src, dst, rows | cols << 32,
@@ -1099,10 +1115,11 @@ TORCH_LIBRARY_FRAGMENT(vinf, m) {
   m.def("masked_gemm_nt(Tensor x, Tensor W, Tensor? b, Tensor(a!) y, int relu, Tensor krange, Tensor? krange256=None) -> ()");
   m.def("masked_gemm_nn(Tensor dy, Tensor W, Tensor? h, Tensor(a!) dx, Tensor krange, bool accumulate=False, Tensor? krange256=None, Tensor? Wt=None) -> ()");
   m.def("masked_gemm_tn(Tensor dy, Tensor x, Tensor(a!) dW, Tensor(b!)? db, Tensor skip) -> ()");
-  m.def("gemm_nt(Tensor x, Tensor W, Tensor? b, Tensor(a!) y, int relu, Tensor(b!)? mask=None) -> ()");
+  m.def("gemm_nt(Tensor x, Tensor W, Tensor? b, Tensor(a!) y, int relu, Tensor(b!)? mask=None, bool mask_lanes=False) -> int");
+  m.def("gemm_mask_lanes_route(int M, int N, int K_fwd, int K_bwd, bool bwd_wt) -> int", &gemm_mask_lanes_route);
   m.def("gemm_nt_f32out(Tensor x, Tensor W, Tensor(a!) y) -> ()");
   m.def("gemm_fp(Tensor A, bool a_kmajor, Tensor B, bool b_kmajor, Tensor? bias, Tensor(a!) C, bool accumulate, Tensor(b!)? dbias=None) -> ()");
-  m.def("gemm_nn(Tensor dy, Tensor W, Tensor? h, Tensor(a!) dx, bool accumulate, Tensor? hbits=None, Tensor? Wt=None) -> ()");
+  m.def("gemm_nn(Tensor dy, Tensor W, Tensor? h, Tensor(a!) dx, bool accumulate, Tensor? hbits=None, Tensor? Wt=None, bool hbits_lanes=False) -> int");
   m.def("transpose_bf16_batched(Tensor desc, int n, int tiles) -> ()");
   m.def("gemm_tn(Tensor dy, Tensor x, Tensor(a!) dW, Tensor(b!)? db) -> ()");
   m.def("gemm_tn_group(Tensor[] dy, Tensor[] x, Tensor(a!)[] dW, Tensor(b!)?[] db, Tensor?[] skip, Tensor?[] cmask) -> ()");

@@ -63,6 +63,10 @@ struct GemmArgs {
   unsigned char* mask_out;     // EPI_BF16 + relu: also write 1(y > 0) bits (staged path only)
   long ld_mask;                // bytes per mask row
   int aux_bits;                // EPI_BF16_RELUMASK: aux is such a bitmask (ld_aux in bytes)
+  // Lane-private bitmask (gemm256 LANES instantiations only; see "Lane-private ReLU mask" below):
+  // mask_out / aux hold the same M*N/8 bytes in MFMA accumulator order instead of row-major.
+  // Set by the launchers after lanes_ok(); the row-major fields above are then unused.
+  int mask_lanes;
   // EPI_CPL_BWD: the input gradient of coupling layer l's conditioner completes
   // gy = dL/dh_{l+1}, which is exactly the output gradient coupling layer l-1 needs. The
   // epilogue finishes gy (= old C + acc, never stored) and applies layer l-1's backward
@@ -296,6 +300,42 @@ __device__ __forceinline__ v4u bf_stage_fix(v4u v, bool swapped) {
   return swapped ? (v4u){v[2], v[3], v[0], v[1]} : v;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Lane-private ReLU mask (gemm256.hip, 256x256 tiles, M % 256 == 0 and N % 256 == 0).
+// The forward product that writes the mask and the input-gradient product that reads it run
+// the same tile / wave / lane mapping over the same [M][N] output, so the bit of acc[i][j][r]
+// never has to leave the lane that holds it. Per tile (tm, tn), wave w = wr*4 + wc and lane l:
+//   16 bytes at  base + (((tm * (N/256) + tn) * 8 + w) * 64 + l) * 16   (M*N/8 bytes in all:
+//   the row-major buffer's size; a wave's 1 KiB is one coalesced access)
+//   dword (j >> 2) * 2 + (i >> 1),  s = (i & 1) * 4 + (j & 3):
+//     r = 0 -> bit 15 - s,  r = 1 -> bit 31 - s,  r = 2 -> bit 7 - s,  r = 3 -> bit 23 - s
+// i.e. the dword is the OR of pos(lo) >> s and pos(hi) >> (8 + s) over its 8 (i, j) pairs, where
+// lo / hi are the packed bf16 pairs (r = 0, 1) / (r = 2, 3) the epilogue stages and pos() leaves
+// bit 15 / 31 set iff that bf16 half is > 0 (sign clear and not +0). Bytes 0..7 belong to
+// accumulator blocks j = 0..3 and bytes 8..15 to j = 4..7, so the persistent kernel's two
+// 64-row epilogue passes each own one 8-byte half. The tile id comes from the tile's
+// coordinates, never from the block that runs it.
+__device__ __forceinline__ unsigned bf_pos_pair(unsigned w) {
+  return ((w & 0x7fff7fffu) + 0x7fff7fffu) & ~w & 0x80008000u;
+}
+__device__ __forceinline__ long lane_mask_off(int N, int m0w, int n0w, int lane) {
+  // m0w / n0w: any row / column of the wave's 128 x 64 sub-tile
+  const int tile = (m0w >> 8) * (N >> 8) + (n0w >> 8);
+  const int wave = ((m0w >> 7) & 1) * 4 + ((n0w >> 6) & 3);
+  return (((long)tile * 8 + wave) * 64 + lane) * 16;
+}
+// all-ones iff the bit of acc[i][j][r] is set in its dword w
+__device__ __forceinline__ unsigned lane_mask_keep(unsigned w, int i, int j, int r) {
+  const int s = (i & 1) * 4 + (j & 3);
+  const int bit = (r == 0 ? 15 : r == 1 ? 31 : r == 2 ? 7 : 23) - s;
+  return (unsigned)((int)(w << (31 - bit)) >> 31);
+}
+// Host side: the shapes / alignment the lane-private layout is defined for.
+inline bool lanes_ok(const GemmArgs& a, const void* mask) {
+  return a.M > 0 && a.N > 0 && a.M % 256 == 0 && a.N % 256 == 0 && mask != nullptr &&
+         ((unsigned long)mask & 15) == 0 && !a.krange && !a.skip;
+}
+
 // LDS-staged epilogue. In the fragment layout one store instruction covers 16 rows x 32 B
 // (bf16) or 16 rows x 64 B (fp32): 16 partial cache lines per instruction, which made the
 // output write, not the MFMAs, the per-tile fixed cost at K <= 1024 (~15 us per 256^2 tile).
@@ -310,10 +350,18 @@ __device__ __forceinline__ v4u bf_stage_fix(v4u v, bool swapped) {
 // ldc % 4 == 0 (fp32) and a 16-B aligned C (checked by the launchers).
 // J0 / NJA: the rows handled are accumulator blocks [J0, J0 + NJ) of a [4][NJA] array (m0 is the
 // origin of block J0), so a caller short of LDS can stage a sub-tile in several calls.
-template <int EPI, int NJ, bool F8 = false, int J0 = 0, int NJA = NJ>
+// LANES (gemm256 only, bf16 operands, full 256x256 tiles): the ReLU mask in the lane-private
+// layout above. EPI_BF16: the bits come from the packed words as they are staged and leave in
+// one 8- or 16-byte store per lane; EPI_BF16_RELUMASK: `lb` holds the lane's 16 mask bytes
+// (loaded by the caller) and is applied to the accumulators as they are staged. Either way the
+// readback loop only writes C.
+template <int EPI, int NJ, bool F8 = false, int J0 = 0, int NJA = NJ, bool LANES = false>
 __device__ __forceinline__ void epi_tile_staged(const GemmArgs& a, const v4f (&acc)[4][NJA],
                                                 int m0, int n0, int split, char* region,
-                                                int lane) {
+                                                int lane, v4u lb = (v4u){0u, 0u, 0u, 0u}) {
+  static_assert(!LANES || (!F8 && (EPI == EPI_BF16 || EPI == EPI_BF16_RELUMASK) &&
+                           (NJ == 4 || NJ == 8) && J0 % 4 == 0),
+                "lane-private mask: bf16 products, whole 64-row passes");
   const int g = lane >> 4, c = lane & 15;
   if constexpr (EPI == EPI_BF16 || EPI == EPI_BF16_RELUMASK) {
     float bv[4][4];
@@ -356,27 +404,49 @@ __device__ __forceinline__ void epi_tile_staged(const GemmArgs& a, const v4f (&a
         smj[j] = a.f8_sa_per_row ? a.f8_sa[m] : a.f8_sa[0];
       }
     }
+    constexpr bool LN_OUT = LANES && EPI == EPI_BF16, LN_IN = LANES && EPI == EPI_BF16_RELUMASK;
+    unsigned mw[NJ / 2 > 0 ? NJ / 2 : 1];   // LN_OUT: this call's dwords of the lane's mask
+#pragma unroll
+    for (int d = 0; d < NJ / 2; ++d) mw[d] = 0u;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int row = j * 16 + c;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        float v0 = fmaf(acc[i][J0 + j][0], smj[j] * sn[i][0], bv[i][0]);
-        float v1 = fmaf(acc[i][J0 + j][1], smj[j] * sn[i][1], bv[i][1]);
-        float v2 = fmaf(acc[i][J0 + j][2], smj[j] * sn[i][2], bv[i][2]);
-        float v3 = fmaf(acc[i][J0 + j][3], smj[j] * sn[i][3], bv[i][3]);
+        float a0 = acc[i][J0 + j][0], a1 = acc[i][J0 + j][1];
+        float a2 = acc[i][J0 + j][2], a3 = acc[i][J0 + j][3];
+        if constexpr (LN_IN) {   // masked accumulators become +0, which stores as bf16 +0
+          const unsigned w = lb[((J0 + j) >> 2) * 2 + (i >> 1)];
+          a0 = __uint_as_float(__float_as_uint(a0) & lane_mask_keep(w, i, J0 + j, 0));
+          a1 = __uint_as_float(__float_as_uint(a1) & lane_mask_keep(w, i, J0 + j, 1));
+          a2 = __uint_as_float(__float_as_uint(a2) & lane_mask_keep(w, i, J0 + j, 2));
+          a3 = __uint_as_float(__float_as_uint(a3) & lane_mask_keep(w, i, J0 + j, 3));
+        }
+        float v0 = fmaf(a0, smj[j] * sn[i][0], bv[i][0]);
+        float v1 = fmaf(a1, smj[j] * sn[i][1], bv[i][1]);
+        float v2 = fmaf(a2, smj[j] * sn[i][2], bv[i][2]);
+        float v3 = fmaf(a3, smj[j] * sn[i][3], bv[i][3]);
         if (relu) { v0 = relu_f(v0); v1 = relu_f(v1); v2 = relu_f(v2); v3 = relu_f(v3); }
         const unsigned lo = (unsigned)f2bf(v0) | ((unsigned)f2bf(v1) << 16);
         const unsigned hi = (unsigned)f2bf(v2) | ((unsigned)f2bf(v3) << 16);
+        if constexpr (LN_OUT) {
+          const int s = (i & 1) * 4 + ((J0 + j) & 3);
+          mw[(j >> 2) * 2 + (i >> 1)] |= (bf_pos_pair(lo) >> s) | (bf_pos_pair(hi) >> (8 + s));
+        }
         const int slot = i * 4 + g;  // 8-B slot of the 128-B row
         *(LDS_AS v2u*)(region + bf_stage_off(row, slot)) = (v2u){lo, hi};
       }
+    }
+    if constexpr (LN_OUT) {   // one coalesced store per lane: no cross-lane work, no byte stores
+      unsigned char* mp = a.mask_out + lane_mask_off(a.N, m0, n0, lane) + (J0 >> 2) * 8;
+      if constexpr (NJ == 8) *reinterpret_cast<v4u*>(mp) = (v4u){mw[0], mw[1], mw[2], mw[3]};
+      else *reinterpret_cast<v2u*>(mp) = (v2u){mw[0], mw[1]};
     }
     // aux rows (ReLU mask) for every readback row, in flight while the LDS writes drain
     const int q = lane & 7;
     uint4 hv[NJ * 2];
     unsigned hb[NJ * 2];
-    if constexpr (EPI == EPI_BF16_RELUMASK) {
+    if constexpr (EPI == EPI_BF16_RELUMASK && !LN_IN) {
       if (a.aux_bits) {
 #pragma unroll
         for (int it = 0; it < NJ * 2; ++it) {
@@ -413,7 +483,7 @@ __device__ __forceinline__ void epi_tile_staged(const GemmArgs& a, const v4f (&a
       const int m = m0 + row, n = n0 + q * 8;
       if (m < a.M && n < a.N) {
         uint4 o = make_uint4(v[0], v[1], v[2], v[3]);
-        if constexpr (EPI == EPI_BF16_RELUMASK) {
+        if constexpr (EPI == EPI_BF16_RELUMASK && !LN_IN) {
           // keep element e iff aux_e > 0 (bf16: sign clear and not +0), per 16-bit half
           // branch-free, both halves at once: bit 15 / 31 of p is set iff that bf16 half is in
           // [1, 0x7fff] (> 0; see the bitmask epilogue below), and (p << 1) - (p >> 15)
@@ -434,7 +504,8 @@ __device__ __forceinline__ void epi_tile_staged(const GemmArgs& a, const v4f (&a
             o.x &= keep(h.x); o.y &= keep(h.y); o.z &= keep(h.z); o.w &= keep(h.w);
           }
         }
-        if (EPI == EPI_BF16 && a.mask_out) {  // 1(y > 0) of the stored bf16, 8 bits per lane
+        // (row-major mask) 1(y > 0) of the stored bf16, 8 bits per lane
+        if (!LN_OUT && EPI == EPI_BF16 && a.mask_out) {
           // branch-free: half h > 0 (bf16) <=> h in [1, 0x7fff] <=> bit 15 of
           // ((h & 0x7fff) + 0x7fff) & ~h; both halves at once (no carry: each sum <= 0xfffe),
           // then bits 15 / 31 of the 4 words gathered to bits 2e / 2e + 1 of one byte

@@ -119,12 +119,22 @@ void nf_launch_sumsq_guard(const float* x, long n, float* partial, int npartial,
 // gemm.hip (bf16 MFMA, fp32 accumulate)
 // mask_out: optional ReLU bitmask [M][N/8] bytes (bit e of byte n/8 <-> column n+e) written by
 // the forward epilogue; aux_is_bits: the dgrad's ReLU mask `aux` is such a bitmask (ld in bytes)
-void nf_launch_gemm_nt(const void* x, long ldx, const void* W, long ldw, const void* bias, void* y,
-                       long ldy, int M, int N, int K, int relu, hipStream_t stream,
-                       void* mask_out = nullptr, long ld_mask = 0);
-void nf_launch_gemm_nn(const void* dy, long lddy, const void* W, long ldw, const void* aux,
-                       long ld_aux, void* dx, long lddx, int dx_is_f32, int accumulate, int M,
-                       int N, int K, hipStream_t stream, int aux_is_bits = 0);
+// Lane-private mask (mask_lanes = 1 / aux_is_bits = 2): the same M*N/8 bytes in the 256x256
+// kernel's accumulator order (gemm_tile.h, "Lane-private ReLU mask"), written and read only by
+// that kernel on whole 256x256 tiles. These launchers return NF_LANES_OK (0) when they launched,
+// and launch nothing otherwise: NF_LANES_SHAPE when the layout is not defined for the shape or
+// alignment (both ends of a product pair then agree, and the caller uses the row-major mode),
+// NF_LANES_KERNEL when the shape fits but the call routes to the 128x128 kernel.
+enum { NF_LANES_OK = 0, NF_LANES_SHAPE = 1, NF_LANES_KERNEL = 2 };
+int nf_launch_gemm_nt(const void* x, long ldx, const void* W, long ldw, const void* bias, void* y,
+                      long ldy, int M, int N, int K, int relu, hipStream_t stream,
+                      void* mask_out = nullptr, long ld_mask = 0, int mask_lanes = 0);
+// what the pair (forward over K_fwd writing the mask, input gradient over K_bwd reading it)
+// would return for lane mode right now, without launching anything
+int nf_gemm_mask_lanes_route(int M, int N, int K_fwd, int K_bwd, int bwd_wt);
+int nf_launch_gemm_nn(const void* dy, long lddy, const void* W, long ldw, const void* aux,
+                      long ld_aux, void* dx, long lddx, int dx_is_f32, int accumulate, int M,
+                      int N, int K, hipStream_t stream, int aux_is_bits = 0);
 // y[M][N] = x W^T with bf16 operands and an fp32 output (no rounding of the accumulator)
 void nf_launch_gemm_nt_f32out(const void* x, long ldx, const void* W, long ldw, float* y, long ldy,
                               int M, int N, int K, hipStream_t stream);
@@ -162,22 +172,22 @@ long nf_gemm_tn_group_workspace(int nprob, const NfTnProblem* pr);
 void nf_launch_gemm_tn_group(int nprob, const NfTnProblem* pr, float* work, hipStream_t stream);
 // gemm256.hip: 256x256 8-phase kernel (forward / input-gradient products)
 // krange: optional per-256-column-tile K ranges [lo, hi) of a MADE-masked weight
-void nf_launch_gemm256_nt(const void* x, long ldx, const void* W, long ldw, const void* bias,
-                          void* y, long ldy, int M, int N, int K, int relu, hipStream_t stream,
-                          void* mask_out = nullptr, long ld_mask = 0,
-                          const int* krange = nullptr);
-void nf_launch_gemm256_nn(const void* dy, long lddy, const void* W, long ldw, const void* aux,
-                          long ld_aux, void* dx, long lddx, int dx_is_f32, int accumulate, int M,
-                          int N, int K, hipStream_t stream, int aux_is_bits = 0,
-                          const int* krange = nullptr, int krange_segs = 1, int w_kmajor = 0);
+int nf_launch_gemm256_nt(const void* x, long ldx, const void* W, long ldw, const void* bias,
+                         void* y, long ldy, int M, int N, int K, int relu, hipStream_t stream,
+                         void* mask_out = nullptr, long ld_mask = 0,
+                         const int* krange = nullptr, int mask_lanes = 0);
+int nf_launch_gemm256_nn(const void* dy, long lddy, const void* W, long ldw, const void* aux,
+                         long ld_aux, void* dx, long lddx, int dx_is_f32, int accumulate, int M,
+                         int N, int K, hipStream_t stream, int aux_is_bits = 0,
+                         const int* krange = nullptr, int krange_segs = 1, int w_kmajor = 0);
 void nf_gemm256_set_persist(int on);
 int nf_gemm256_get_persist();
 int nf_gemm256_set_reserve(int cus);   // cus < 0: query; returns the previous value
 int nf_gemm256_set_pair(int mode);     // MADE tile pairing 0 off / 1 auto / 2 always; < 0: query
 // input gradient with W given transposed (Wt [N][K]): NT instantiation, bf16 (ReLU-mask) epilogue
-void nf_launch_gemm256_nt_dgrad(const void* dy, long lddy, const void* Wt, long ldwt,
-                                const void* aux, long ld_aux, int aux_is_bits, void* dx,
-                                long lddx, int M, int N, int K, hipStream_t stream);
+int nf_launch_gemm256_nt_dgrad(const void* dy, long lddy, const void* Wt, long ldwt,
+                               const void* aux, long ld_aux, int aux_is_bits, void* dx,
+                               long lddx, int M, int N, int K, hipStream_t stream);
 // layout.hip: batched bf16 transposes (TrDesc table on the device)
 void nf_launch_transpose_bf16_batched(const void* desc, int n, int total_tiles,
                                       hipStream_t stream);

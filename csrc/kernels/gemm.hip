@@ -392,16 +392,32 @@ static bool use_256(int M, int N, int K) {
 
 bool nf_gemm_prefer_256(int M, int N, int K) { return use_256(M, N, K); }
 
+// Would a forward product [M][N] over K_fwd writing a lane-private ReLU mask and the input
+// gradient [M][N] over K_bwd reading it both take the lane mode under the current kernel choice?
+// (bwd_wt: the input gradient gets W^T and always runs the 256x256 NT kernel)
+int nf_gemm_mask_lanes_route(int M, int N, int K_fwd, int K_bwd, int bwd_wt) {
+  if (M <= 0 || N <= 0 || M % 256 || N % 256) return NF_LANES_SHAPE;
+  if (!use_256(M, N, K_fwd) || (!bwd_wt && !use_256(M, N, K_bwd))) return NF_LANES_KERNEL;
+  return NF_LANES_OK;
+}
+
 static bool use_256_tn() { return g_tile_mode == 3; }
 
 // y[M][N] = act(x[M][K] W[N][K]^T + bias)   -> bf16
-void nf_launch_gemm_nt(const void* x, long ldx, const void* W, long ldw, const void* bias, void* y,
-                       long ldy, int M, int N, int K, int relu, hipStream_t stream,
-                       void* mask_out, long ld_mask) {
-  if (M <= 0 || N <= 0) return;
+int nf_launch_gemm_nt(const void* x, long ldx, const void* W, long ldw, const void* bias, void* y,
+                      long ldy, int M, int N, int K, int relu, hipStream_t stream,
+                      void* mask_out, long ld_mask, int mask_lanes) {
+  if (mask_lanes) {   // the lane-private mask belongs to the 256x256 kernel alone
+    if (M <= 0 || N <= 0 || M % 256 || N % 256 || !mask_out || ((unsigned long)mask_out & 15))
+      return NF_LANES_SHAPE;
+    if (!use_256(M, N, K)) return NF_LANES_KERNEL;
+    return nf_launch_gemm256_nt(x, ldx, W, ldw, bias, y, ldy, M, N, K, relu, stream, mask_out,
+                                ld_mask, nullptr, 1);
+  }
+  if (M <= 0 || N <= 0) return 0;
   if (use_256(M, N, K)) {
     nf_launch_gemm256_nt(x, ldx, W, ldw, bias, y, ldy, M, N, K, relu, stream, mask_out, ld_mask);
-    return;
+    return 0;
   }
   GemmArgs a{};
   a.A = (const bf16_t*)x; a.lda = ldx;
@@ -411,6 +427,7 @@ void nf_launch_gemm_nt(const void* x, long ldx, const void* W, long ldw, const v
   a.M = M; a.N = N; a.K = K; a.k_per_split = ((K + BK - 1) / BK) * BK; a.relu = relu;
   a.mask_out = (unsigned char*)mask_out; a.ld_mask = ld_mask;
   launch<true, true, EPI_BF16>(a, 1, stream);
+  return 0;
 }
 
 // y[M][N] = x[M][K] W[N][K]^T -> fp32 (the module layers' bf16 precision path: bf16 operands,
@@ -427,14 +444,21 @@ void nf_launch_gemm_nt_f32out(const void* x, long ldx, const void* W, long ldw, 
 }
 
 // dx[M][N] = dy[M][K] W[K][N]  (* 1(aux>0) -> bf16)  or  (fp32 dx (+)= ...)
-void nf_launch_gemm_nn(const void* dy, long lddy, const void* W, long ldw, const void* aux,
-                       long ld_aux, void* dx, long lddx, int dx_is_f32, int accumulate, int M,
-                       int N, int K, hipStream_t stream, int aux_is_bits) {
-  if (M <= 0 || N <= 0) return;
+int nf_launch_gemm_nn(const void* dy, long lddy, const void* W, long ldw, const void* aux,
+                      long ld_aux, void* dx, long lddx, int dx_is_f32, int accumulate, int M,
+                      int N, int K, hipStream_t stream, int aux_is_bits) {
+  if (aux_is_bits == 2) {   // lane-private bits: the 256x256 kernel alone
+    if (M <= 0 || N <= 0 || M % 256 || N % 256 || !aux || ((unsigned long)aux & 15) || dx_is_f32)
+      return NF_LANES_SHAPE;
+    if (!use_256(M, N, K)) return NF_LANES_KERNEL;
+    return nf_launch_gemm256_nn(dy, lddy, W, ldw, aux, ld_aux, dx, lddx, dx_is_f32, accumulate, M,
+                                N, K, stream, 2);
+  }
+  if (M <= 0 || N <= 0) return 0;
   if (use_256(M, N, K)) {
     nf_launch_gemm256_nn(dy, lddy, W, ldw, aux, ld_aux, dx, lddx, dx_is_f32, accumulate, M, N, K,
                          stream, aux_is_bits);
-    return;
+    return 0;
   }
   GemmArgs a{};
   a.A = (const bf16_t*)dy; a.lda = lddy;
@@ -451,6 +475,7 @@ void nf_launch_gemm_nn(const void* dy, long lddy, const void* W, long ldw, const
   } else {
     launch<true, false, EPI_BF16>(a, 1, stream);
   }
+  return 0;
 }
 
 long nf_gemm_tn_workspace(int M, int N, int splits) {

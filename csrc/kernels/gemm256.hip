@@ -469,7 +469,8 @@ __device__ __forceinline__ void epi_coupling_fwd(const GemmArgs& a, const v4f (&
 // of 128 bytes in place of the two bf16 16x16x32 steps - the same LDS image and fragment reads
 // (a lane's 32 k-bytes are the chunks g and g + 4 the bf16 steps read), 2x the FLOPs per
 // MFMA cycle; block scales fixed at 2^0, the per-row / per-tensor scales applied in the epilogue.
-template <bool A_KMAJOR, bool B_KMAJOR, int EPI, int D, bool DB, bool F8, bool DODB>
+template <bool A_KMAJOR, bool B_KMAJOR, int EPI, int D, bool DB, bool F8, bool DODB,
+          bool LANES = false>
 __device__ __forceinline__ void gemm256_body_impl(const GemmArgs& a, int wg, int split,
                                                   char* smem) {
   constexpr int BKE = F8 ? 2 * BK : BK;  // K-tile in elements
@@ -703,8 +704,17 @@ __device__ __forceinline__ void gemm256_body_impl(const GemmArgs& a, int wg, int
   }
   if (a.staged) {
     barrier();  // every wave is past its last operand read; each wave reuses 16 KiB of LDS
-    epi_tile_staged<EPI, 8, F8>(a, acc, m0 + wr * 128, n0 + wc * 64, split, smem + wave * 16384,
-                                lane_e);
+    if constexpr (LANES) {   // lane-private ReLU mask (gemm_tile.h): the lane's 16 mask bytes
+      v4u lb = (v4u){0u, 0u, 0u, 0u};
+      if constexpr (EPI == EPI_BF16_RELUMASK)
+        lb = *reinterpret_cast<const v4u*>(
+            (const char*)a.aux + lane_mask_off(a.N, m0 + wr * 128, n0 + wc * 64, lane_e));
+      epi_tile_staged<EPI, 8, false, 0, 8, true>(a, acc, m0 + wr * 128, n0 + wc * 64, split,
+                                                 smem + wave * 16384, lane_e, lb);
+    } else {
+      epi_tile_staged<EPI, 8, F8>(a, acc, m0 + wr * 128, n0 + wc * 64, split,
+                                  smem + wave * 16384, lane_e);
+    }
 #ifdef NF_G256_STAMPS
     NF_STAMP(3);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -725,7 +735,8 @@ __device__ __forceinline__ void gemm256_body_impl(const GemmArgs& a, int wg, int
   }
 }
 
-template <bool A_KMAJOR, bool B_KMAJOR, int EPI, int D, bool DB, bool F8 = false>
+template <bool A_KMAJOR, bool B_KMAJOR, int EPI, int D, bool DB, bool F8 = false,
+          bool LANES = false>
 __device__ __forceinline__ void gemm256_body(const GemmArgs& a, int wg, int split, char* smem) {
   if constexpr (DB) {
     const int ntn = (a.N + BN - 1) / BN;
@@ -734,7 +745,7 @@ __device__ __forceinline__ void gemm256_body(const GemmArgs& a, int wg, int spli
       return;
     }
   }
-  gemm256_body_impl<A_KMAJOR, B_KMAJOR, EPI, D, DB, F8, false>(a, wg, split, smem);
+  gemm256_body_impl<A_KMAJOR, B_KMAJOR, EPI, D, DB, F8, false, LANES>(a, wg, split, smem);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -771,9 +782,10 @@ __device__ __forceinline__ void gemm256_body(const GemmArgs& a, int wg, int spli
 // starts late delays one tile, not a list). Every block increments the done counter once, as it
 // finishes; the last one zeroes the slot for the next launch that uses it. No block ever waits
 // on another (no spin), so the grid always drains.
-template <bool A_KMAJOR, bool B_KMAJOR, int EPI, bool DYN = false>
+template <bool A_KMAJOR, bool B_KMAJOR, int EPI, bool DYN = false, bool LANES = false>
 __device__ __forceinline__ void gemm256_persistent_body(const GemmArgs& a, char* smem) {
   static_assert(!(DYN && EPI == EPI_CPL_FWD), "the coupling forward reads other waves' staging");
+  static_assert(!LANES || EPI == EPI_BF16 || EPI == EPI_BF16_RELUMASK, "lane-private ReLU mask");
   constexpr int D = 4, NSLOT = 8;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -994,6 +1006,26 @@ __device__ __forceinline__ void gemm256_persistent_body(const GemmArgs& a, char*
     // the next tile's K-tile 0 and K-tile 1's A-lo / B-lo: stream halves 4T .. 4T+5, i.e. the
     // slots of K-tiles T-2 (all four, read long ago) and T-1's A-lo / B-lo (read in its phase
     // r1) - not the free pair the epilogue stages through
+    const int fs = (4 * (T - 1) + 2) & (NSLOT - 1);   // free slot pair of the last K-tile
+    char* region = wave < 4 ? smem + fs * HALF_BYTES + wave * 8192
+                            : smem + NSLOT * HALF_BYTES + (wave - 4) * 8192;
+    // Lane-private ReLU mask (gemm_tile.h): the wave's 1 KiB of mask bytes goes out here, AHEAD
+    // of the burst - vmcnt retires in issue order, so the counted wait in front of the epilogue
+    // covers this one load and none of the next tile's twelve. It lands in the head of the
+    // wave's own staging region (LDS DMA: no register is written behind the compiler's back)
+    // and each lane reads its 16 bytes back before it stages anything. WAR on the slot pair:
+    // the other row group is at most one barrier behind, i.e. past the lgkmcnt(0) of the last
+    // K-tile's phase r3, its last read of these slots; the DMA stream restages them only in
+    // the next tile's phases 1 / 2.
+    if constexpr (LANES && EPI == EPI_BF16_RELUMASK) {
+      int zl;   // (an opaque zero, as for the epilogue's offsets below: nothing to hoist)
+      asm volatile("s_mov_b32 %0, 0" : "=s"(zl));
+      const char* src =
+          (const char*)a.aux + lane_mask_off(a.N, m0 + wr * 128, n0 + wc * 64, lane + zl);
+      const unsigned lds = (unsigned)(unsigned long)(LDS_AS char*)region;
+      asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off"
+                   :: "v"(src), "s"(lds) : "memory", "m0");
+    }
     int m0n = 0, n0n = 0;
     if (has_next) {
       if constexpr (DYN) tile_at(id_next, m0n, n0n);
@@ -1008,9 +1040,6 @@ __device__ __forceinline__ void gemm256_persistent_body(const GemmArgs& a, char*
     }
     if (wr == 0) barrier();
     // ---- epilogue of tile s through the free LDS (see above)
-    const int fs = (4 * (T - 1) + 2) & (NSLOT - 1);   // free slot pair of the last K-tile
-    char* region = wave < 4 ? smem + fs * HALF_BYTES + wave * 8192
-                            : smem + NSLOT * HALF_BYTES + (wave - 4) * 8192;
     // the epilogue's lane-derived offsets from an opaque per-tile zero: hoisted above the tile
     // loop they stayed live across the MFMA loop at the 256-VGPR limit and were spilled
     int zt;
@@ -1025,12 +1054,21 @@ __device__ __forceinline__ void gemm256_persistent_body(const GemmArgs& a, char*
                           lane_e, tid_e);
     } else if constexpr (EPI == EPI_BF16 || EPI == EPI_BF16_RELUMASK) {
       // (DYN: offsets from the opaque lane too, else the claim's register spills them)
-      const int lane_b = DYN ? lane_e : lane;
-      epi_tile_staged<EPI, 4, false, 0, 8>(a, acc, m0 + wr * 128, n0 + wc * 64, 0, region,
-                                           lane_b);
+      const int lane_b = (DYN || LANES) ? lane_e : lane;
+      v4u lb = (v4u){0u, 0u, 0u, 0u};
+      if constexpr (LANES && EPI == EPI_BF16_RELUMASK) {
+        // the mask load is the oldest access in flight: behind it only the burst's twelve
+        // (and, DYN, one claim), so vmcnt(12) retires it and leaves the burst in flight
+        if (has_next) vmwait<12>();
+        else vmwait<0>();
+        lb = *(const LDS_AS v4u*)(region + lane_b * 16);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // read before staging overwrites it
+      }
+      epi_tile_staged<EPI, 4, false, 0, 8, LANES>(a, acc, m0 + wr * 128, n0 + wc * 64, 0, region,
+                                                  lane_b, lb);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // own readback done before re-staging
-      epi_tile_staged<EPI, 4, false, 4, 8>(a, acc, m0 + wr * 128 + 64, n0 + wc * 64, 0, region,
-                                           lane_b);
+      epi_tile_staged<EPI, 4, false, 4, 8, LANES>(a, acc, m0 + wr * 128 + 64, n0 + wc * 64, 0,
+                                                  region, lane_b, lb);
     } else {
       epi_tile_staged<EPI, 8>(a, acc, m0 + wr * 128, n0 + wc * 64, 0, region, lane_e);
     }
@@ -1055,11 +1093,11 @@ __device__ __forceinline__ void gemm256_persistent_body(const GemmArgs& a, char*
   }
 }
 
-template <bool A_KMAJOR, bool B_KMAJOR, int EPI, bool DYN = false>
+template <bool A_KMAJOR, bool B_KMAJOR, int EPI, bool DYN = false, bool LANES = false>
 __global__ void __launch_bounds__(NTHR, 1) gemm256_persistent_kernel(GemmArgs a) {
   __shared__ __attribute__((aligned(16))) char smem[8 * HALF_BYTES + 8 * 4096];
   NF_STAMP(5);   // stamps build: block start / end (the body ends on vmcnt(0) + barrier)
-  gemm256_persistent_body<A_KMAJOR, B_KMAJOR, EPI, DYN>(a, smem);
+  gemm256_persistent_body<A_KMAJOR, B_KMAJOR, EPI, DYN, LANES>(a, smem);
   NF_STAMP(6);
 }
 
@@ -1072,13 +1110,14 @@ __device__ __forceinline__ int krange_len(const GemmArgs& a, int tn) {
   return len;
 }
 
-template <bool A_KMAJOR, bool B_KMAJOR, int EPI, int D, bool DB, bool F8 = false>
+template <bool A_KMAJOR, bool B_KMAJOR, int EPI, int D, bool DB, bool F8 = false,
+          bool LANES = false>
 __global__ void __launch_bounds__(NTHR, 1) gemm256_kernel(GemmArgs a) {
   __shared__ __attribute__((aligned(16))) char smem[smem_bytes(D)];
   const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
-  if (!a.pair_tiles) {
-    gemm256_body<A_KMAJOR, B_KMAJOR, EPI, D, DB, F8>(a, xcd_remap(blockIdx.x, ntm * ntn),
-                                                      blockIdx.y, smem);
+  if (LANES || !a.pair_tiles) {   // (the lane-private mask excludes MADE K ranges, hence pairs)
+    gemm256_body<A_KMAJOR, B_KMAJOR, EPI, D, DB, F8, LANES>(a, xcd_remap(blockIdx.x, ntm * ntn),
+                                                             blockIdx.y, smem);
     return;
   }
   // MADE-masked products: column tiles stream very different K lengths (a triangular mask:
@@ -1238,9 +1277,14 @@ inline bool pair_ok(const GemmArgs& a, int ntm, int ntn, int splits) {
          (g_pair == 2 || (long)ntm * (ntn / 2) >= device_cus_256());
 }
 
-template <bool AK, bool BK_, int EPI, bool DB = false>
+template <bool AK, bool BK_, int EPI, bool DB = false, bool LANES = false>
 void launch(GemmArgs a, int splits, hipStream_t stream) {
   a.staged = staged_ok(a, EPI);
+  if (LANES && (!a.staged || !a.mask_lanes)) {   // (callers check lanes_ok() first)
+    fprintf(stderr, "vinf: lane-private ReLU mask needs whole 256x256 tiles and the staged "
+                    "epilogue\n");
+    abort();
+  }
   if (a.mask_out && !a.staged) {
     fprintf(stderr, "vinf: ReLU bitmask output needs the staged epilogue (N %% 8, 16-B rows)\n");
     abort();
@@ -1266,25 +1310,26 @@ void launch(GemmArgs a, int splits, hipStream_t stream) {
       if (g_persist == 2 && g_qctr && hipGetDevice(&dev) == hipSuccess && dev == g_qctr_dev) {
         a.qctr = claim_slot(stream);
         if (a.qctr)
-          hipLaunchKernelGGL((gemm256_persistent_kernel<AK, BK_, EPI, true>), dim3(G),
+          hipLaunchKernelGGL((gemm256_persistent_kernel<AK, BK_, EPI, true, LANES>), dim3(G),
                              dim3(NTHR), 0, stream, a);
         else   // capture pool used up: fixed tile lists
-          hipLaunchKernelGGL((gemm256_persistent_kernel<AK, BK_, EPI>), dim3(G), dim3(NTHR), 0,
-                             stream, a);
+          hipLaunchKernelGGL((gemm256_persistent_kernel<AK, BK_, EPI, false, LANES>), dim3(G),
+                             dim3(NTHR), 0, stream, a);
         NF_HIP_CHECK(hipGetLastError());
         return;
       }
     }
     if (g_persist == 1) {
-      hipLaunchKernelGGL((gemm256_persistent_kernel<AK, BK_, EPI>), dim3(G), dim3(NTHR), 0,
-                         stream, a);
+      hipLaunchKernelGGL((gemm256_persistent_kernel<AK, BK_, EPI, false, LANES>), dim3(G),
+                         dim3(NTHR), 0, stream, a);
       NF_HIP_CHECK(hipGetLastError());
       return;
     }
   }
   }
   dim3 grid(a.pair_tiles ? ntm * (ntn / 2) : ntm * ntn, splits), block(NTHR);
-  hipLaunchKernelGGL((gemm256_kernel<AK, BK_, EPI, 4, DB>), grid, block, 0, stream, a);
+  hipLaunchKernelGGL((gemm256_kernel<AK, BK_, EPI, 4, DB, false, LANES>), grid, block, 0, stream,
+                     a);
   NF_HIP_CHECK(hipGetLastError());
 }
 
@@ -1342,10 +1387,12 @@ int nf_gemm256_xcd_pack(int on) {   // on < 0: query; returns the previous setti
 int nf_gemm256_get_persist() { return g256::g_persist; }
 
 // y[M][N] = act(x[M][K] W[N][K]^T + bias) -> bf16
-void nf_launch_gemm256_nt(const void* x, long ldx, const void* W, long ldw, const void* bias,
-                          void* y, long ldy, int M, int N, int K, int relu, hipStream_t stream,
-                          void* mask_out, long ld_mask, const int* krange) {
-  if (M <= 0 || N <= 0) return;
+// mask_lanes: mask_out in the lane-private layout (gemm_tile.h). Returns 0 when launched, 1 when
+// lane mode was asked for on a shape it is not defined for (nothing is launched then).
+int nf_launch_gemm256_nt(const void* x, long ldx, const void* W, long ldw, const void* bias,
+                         void* y, long ldy, int M, int N, int K, int relu, hipStream_t stream,
+                         void* mask_out, long ld_mask, const int* krange, int mask_lanes) {
+  if (M <= 0 || N <= 0) return mask_lanes ? NF_LANES_SHAPE : NF_LANES_OK;
   GemmArgs a{};
   a.A = (const nf::bf16_t*)x; a.lda = ldx;
   a.B = (const nf::bf16_t*)W; a.ldb = ldw;
@@ -1354,15 +1401,24 @@ void nf_launch_gemm256_nt(const void* x, long ldx, const void* W, long ldw, cons
   a.M = M; a.N = N; a.K = K; a.k_per_split = ((K + 63) / 64) * 64; a.relu = relu;
   a.mask_out = (unsigned char*)mask_out; a.ld_mask = ld_mask;
   a.krange = krange;
+  if (mask_lanes) {
+    if (!relu || !lanes_ok(a, mask_out) || !staged_ok(a, EPI_BF16)) return NF_LANES_SHAPE;
+    a.mask_lanes = 1;
+    g256::launch<true, true, EPI_BF16, false, true>(a, 1, stream);
+    return 0;
+  }
   g256::launch<true, true, EPI_BF16>(a, 1, stream);
+  return 0;
 }
 
 // dx[M][N] = dy[M][K] W[K][N]  (* 1(aux>0) -> bf16)  or  fp32 dx (+)= ...
-void nf_launch_gemm256_nn(const void* dy, long lddy, const void* W, long ldw, const void* aux,
-                          long ld_aux, void* dx, long lddx, int dx_is_f32, int accumulate, int M,
-                          int N, int K, hipStream_t stream, int aux_is_bits, const int* krange,
-                          int krange_segs, int w_kmajor) {
-  if (M <= 0 || N <= 0) return;
+// aux_is_bits == 2: the ReLU bits in the lane-private layout (gemm_tile.h). Returns 0 when
+// launched, 1 when that layout is not defined for the call (nothing is launched then).
+int nf_launch_gemm256_nn(const void* dy, long lddy, const void* W, long ldw, const void* aux,
+                         long ld_aux, void* dx, long lddx, int dx_is_f32, int accumulate, int M,
+                         int N, int K, hipStream_t stream, int aux_is_bits, const int* krange,
+                         int krange_segs, int w_kmajor) {
+  if (M <= 0 || N <= 0) return aux_is_bits == 2 ? NF_LANES_SHAPE : NF_LANES_OK;
   GemmArgs a{};
   a.krange = krange;
   a.krange_segs = krange_segs;
@@ -1372,6 +1428,13 @@ void nf_launch_gemm256_nn(const void* dy, long lddy, const void* W, long ldw, co
   a.aux = (const nf::bf16_t*)aux; a.ld_aux = ld_aux;
   a.aux_bits = aux_is_bits;
   a.M = M; a.N = N; a.K = K; a.k_per_split = ((K + 63) / 64) * 64;
+  if (aux_is_bits == 2) {
+    if (dx_is_f32 || !lanes_ok(a, aux) || !staged_ok(a, EPI_BF16_RELUMASK)) return NF_LANES_SHAPE;
+    a.mask_lanes = 1;
+    if (w_kmajor) g256::launch<true, true, EPI_BF16_RELUMASK, false, true>(a, 1, stream);
+    else g256::launch<true, false, EPI_BF16_RELUMASK, false, true>(a, 1, stream);
+    return 0;
+  }
   if (w_kmajor) {   // W given as Wt [N][K]: the NT instantiation (k-major fragment reads)
     if (dx_is_f32) {
       if (accumulate) g256::launch<true, true, EPI_F32_ACC>(a, 1, stream);
@@ -1381,7 +1444,7 @@ void nf_launch_gemm256_nn(const void* dy, long lddy, const void* W, long ldw, co
     } else {
       g256::launch<true, true, EPI_BF16>(a, 1, stream);
     }
-    return;
+    return 0;
   }
   if (dx_is_f32) {
     if (accumulate) g256::launch<true, false, EPI_F32_ACC>(a, 1, stream);
@@ -1391,15 +1454,17 @@ void nf_launch_gemm256_nn(const void* dy, long lddy, const void* W, long ldw, co
   } else {
     g256::launch<true, false, EPI_BF16>(a, 1, stream);
   }
+  return 0;
 }
 
 // Input gradient dx[M][N] = dy[M][K] W[K][N] with W given transposed (Wt [N][K], k-major):
 // the NT instantiation (b128 fragment reads of both operands) with the bf16 ReLU-mask (aux =
-// activation or bitmask) or plain bf16 epilogue.
-void nf_launch_gemm256_nt_dgrad(const void* dy, long lddy, const void* Wt, long ldwt,
-                                const void* aux, long ld_aux, int aux_is_bits, void* dx,
-                                long lddx, int M, int N, int K, hipStream_t stream) {
-  if (M <= 0 || N <= 0) return;
+// activation or bitmask; aux_is_bits == 2: lane-private bits, return value as above) or plain
+// bf16 epilogue.
+int nf_launch_gemm256_nt_dgrad(const void* dy, long lddy, const void* Wt, long ldwt,
+                               const void* aux, long ld_aux, int aux_is_bits, void* dx,
+                               long lddx, int M, int N, int K, hipStream_t stream) {
+  if (M <= 0 || N <= 0) return aux_is_bits == 2 ? NF_LANES_SHAPE : NF_LANES_OK;
   GemmArgs a{};
   a.A = (const nf::bf16_t*)dy; a.lda = lddy;
   a.B = (const nf::bf16_t*)Wt; a.ldb = ldwt;
@@ -1407,8 +1472,15 @@ void nf_launch_gemm256_nt_dgrad(const void* dy, long lddy, const void* Wt, long 
   a.aux = (const nf::bf16_t*)aux; a.ld_aux = ld_aux;
   a.aux_bits = aux_is_bits;
   a.M = M; a.N = N; a.K = K; a.k_per_split = ((K + 63) / 64) * 64;
+  if (aux_is_bits == 2) {
+    if (!lanes_ok(a, aux) || !staged_ok(a, EPI_BF16_RELUMASK)) return NF_LANES_SHAPE;
+    a.mask_lanes = 1;
+    g256::launch<true, true, EPI_BF16_RELUMASK, false, true>(a, 1, stream);
+    return 0;
+  }
   if (aux) g256::launch<true, true, EPI_BF16_RELUMASK>(a, 1, stream);
   else g256::launch<true, true, EPI_BF16>(a, 1, stream);
+  return 0;
 }
 
 // Last conditioner product of coupling layer l with its coupling forward fused (EPI_CPL_FWD):

@@ -94,9 +94,10 @@ class RealNVPConfig:
         return 6.0 * macs * self.n_layers
 
 
-def _layer_shapes(cfg: RealNVPConfig):
-    """(out, in) of each conditioner linear, padded: in0 = half_pad, out_last = out_pad."""
-    H = cfg.hidden
+def _layer_shapes(cfg: RealNVPConfig, H: int | None = None):
+    """(out, in) of each conditioner linear, padded: in0 = half_pad, out_last = out_pad; H: the
+    hidden width as stored (RealNVPVI.Hp), default the model's own."""
+    H = cfg.hidden if H is None else H
     dims = [cfg.half_pad] + [H] * cfg.n_hidden + [cfg.out_pad]
     return [(dims[i + 1], dims[i]) for i in range(len(dims) - 1)]
 
@@ -127,7 +128,15 @@ class RealNVPVI(FlatEngine):
         L = cfg.n_layers
         layout = FlatLayout()
         layout.add_unit([("base.mu", (cfg.dim,)), ("base.logvar", (cfg.dim,))])
-        self.shapes = _layer_shapes(cfg)
+        # Hidden width as stored. The MFMA products need K % 32 == 0, so a bf16 GPU engine rounds
+        # the hidden layers up to k_align with units whose weights and biases are zero and stay
+        # zero (init_params): their pre-activation is 0, ReLU keeps 0, the mask bit is clear, so
+        # every gradient into or out of them is 0 and so is every optimizer update. The model is
+        # the hidden-wide one; widths already on the grid (every shipped preset) are untouched.
+        a = max(1, cfg.k_align)
+        pad = self.device.type == "cuda" and self.cdt == torch.bfloat16
+        self.Hp = (cfg.hidden + a - 1) // a * a if pad else cfg.hidden
+        self.shapes = _layer_shapes(cfg, self.Hp)
         for l in range(L):
             ts = []
             for i, (o, inp) in enumerate(self.shapes):
@@ -143,7 +152,7 @@ class RealNVPVI(FlatEngine):
     # ------------------------------------------------------------------ setup
     def _alloc_workspace(self):
         cfg, B, dev = self.cfg, self.B, self.device
-        L, Dh, H, D = cfg.n_layers, cfg.half, cfg.hidden, cfg.dim
+        L, Dh, H, D = cfg.n_layers, cfg.half, self.Hp, cfg.dim
         f32 = torch.float32
         self.z0 = torch.empty(B, D, dtype=f32, device=dev)
         self.eps0 = torch.empty(B, D, dtype=f32, device=dev)
@@ -158,6 +167,13 @@ class RealNVPVI(FlatEngine):
         kp = cfg.paths if cfg.paths is not None else KernelPaths.from_env()
         if dev.type == "cuda" and H % 8 == 0:
             self.Mk = torch.empty(L, cfg.n_hidden, B, H // 8, dtype=torch.uint8, device=dev)
+        # ... kept in the 256x256 kernel's lane-private order (gemm_tile.h) where that kernel runs
+        # both the product that writes a mask and the one that reads it: same bytes, no row-major
+        # gather / scatter in either epilogue. Decided per hidden layer at each forward
+        # (_mask_lanes), used by both passes of the step.
+        self.mk_lanes_path = (self.Mk is not None and kp.relu_mask_lanes
+                              and B % 256 == 0 and H % 256 == 0)
+        self.mk_lanes = [False] * cfg.n_hidden
         # per-layer conditioner outputs [s_hat | t] (compute dtype): the backward recomputes
         # s = scale * tanh(s_hat) from them instead of reading a saved fp32 s
         self.ST = torch.empty(L, B, Np, dtype=self.cdt, device=dev)
@@ -254,12 +270,20 @@ class RealNVPVI(FlatEngine):
         P = self.params
         n_lin = len(self.shapes)
         Dh, No = self.cfg.half, 2 * self.cfg.half
+        H, Hp = self.cfg.hidden, self.Hp
         for l in range(self.cfg.n_layers):
             for i, (o, inp) in enumerate(self.shapes):
-                fan_in = Dh if i == 0 else inp
+                # drawn at the model's own hidden width (the same stream as an unpadded engine),
+                # then set into the stored shape: padded hidden units get zero rows / columns
+                ro = H if i < n_lin - 1 else o
+                ri = H if i > 0 else inp
+                fan_in = Dh if i == 0 else ri
                 std = math.sqrt(2.0 / fan_in) if i < n_lin - 1 else self.cfg.init_out_std
-                W = torch.randn(o, inp, generator=g) * std
-                b = torch.randn(o, generator=g) * (0.01 if i < n_lin - 1 else self.cfg.init_out_std)
+                W = torch.zeros(o, inp)
+                b = torch.zeros(o)
+                W[:ro, :ri] = torch.randn(ro, ri, generator=g) * std
+                b[:ro] = torch.randn(ro, generator=g) * (0.01 if i < n_lin - 1
+                                                         else self.cfg.init_out_std)
                 if i == 0:
                     W[:, Dh:] = 0.0          # padded input columns
                 if i == n_lin - 1:
@@ -304,6 +328,19 @@ class RealNVPVI(FlatEngine):
             self.beta.fill_(1.0)
 
     # ------------------------------------------------------------------ forward
+    def _mask_lanes(self):
+        """Which hidden layers keep their ReLU mask lane-private this step: the forward product
+        (K = the layer's input width) and the input gradient that reads the mask (K = the next
+        layer's output width) must both run the 256x256 kernel."""
+        cfg = self.cfg
+        self.mk_lanes = [False] * cfg.n_hidden
+        if not (self.mk_lanes_path and gemm.backend() == "mfma" and self.cdt == torch.bfloat16):
+            return
+        wt = self.wt_dgrad and self.wgrad_stream is None   # _backward_deferred passes Wt
+        for i in range(cfg.n_hidden):
+            k_fwd, k_bwd = self.shapes[i][1], self.shapes[i + 1][0]
+            self.mk_lanes[i] = gemm.mask_lanes_route(self.B, self.Hp, k_fwd, k_bwd, wt)
+
     def _conditioner_hidden(self, l: int, inp: torch.Tensor) -> torch.Tensor:
         """The ReLU hidden layers of layer l's conditioner; returns the last one's output."""
         P = self.params
@@ -311,7 +348,8 @@ class RealNVPVI(FlatEngine):
         for i in range(self.cfg.n_hidden):
             out = self.Act[l, i]
             gemm.linear_fwd(a, P.c(f"l{l}.W{i}"), P.c(f"l{l}.b{i}"), out, relu=True,
-                            mask_out=None if self.Mk is None else self.Mk[l, i])
+                            mask_out=None if self.Mk is None else self.Mk[l, i],
+                            mask_lanes=self.mk_lanes[i])
             a = out
         return a
 
@@ -347,6 +385,7 @@ class RealNVPVI(FlatEngine):
         cfg, P = self.cfg, self.params
         L, nh = cfg.n_layers, cfg.n_hidden
         fuse = self.cf_fuse and gemm.backend() == "mfma"
+        self._mask_lanes()
         for l in range(L):
             ybf = self.Hbf[l + 1] if l + 1 < L else None
             if fuse:
@@ -451,7 +490,8 @@ class RealNVPVI(FlatEngine):
                     nd = self.dHL[l, i - 1]
                     gemm.linear_dgrad(d, P.c(f"l{l}.W{i}"), nd, relu_of=self.Act[l, i - 1],
                                       relu_bits=None if self.Mk is None else self.Mk[l, i - 1],
-                                      Wt=None if WT is None else WT[l][i])
+                                      Wt=None if WT is None else WT[l][i],
+                                      bits_lanes=self.mk_lanes[i - 1])
                     d = nd
                 elif fuse and l > 0:
                     # dL/dh_{l+1} = G[l+1] + d W0 is finished and consumed by layer l-1's
@@ -494,7 +534,8 @@ class RealNVPVI(FlatEngine):
                 if i > 0:
                     nd = dH[i - 1]
                     gemm.linear_dgrad(d, P.c(f"l{l}.W{i}"), nd, relu_of=self.Act[l, i - 1],
-                                      relu_bits=None if self.Mk is None else self.Mk[l, i - 1])
+                                      relu_bits=None if self.Mk is None else self.Mk[l, i - 1],
+                                      bits_lanes=self.mk_lanes[i - 1])
                     d = nd
                 else:
                     gemm.linear_dgrad(d, P.c(f"l{l}.W0"), self._G[l + 1], accumulate=True)
@@ -584,6 +625,7 @@ class RealNVPVI(FlatEngine):
         top[:, :Dh].copy_(self.h(L))
         fuse = self.cf_fuse and gemm.backend() == "mfma"
         P, nh = self.params, cfg.n_hidden
+        self._mask_lanes()
         for l in range(L - 1, -1, -1):
             nxt = self.Hbf[l - 1] if l > 0 else None
             if fuse:

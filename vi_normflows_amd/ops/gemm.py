@@ -59,14 +59,43 @@ def _mfma_ok(*ts) -> bool:
     return True
 
 
+LANES_OK, LANES_SHAPE, LANES_KERNEL = 0, 1, 2   # csrc/include/launchers.h NF_LANES_*
+
+
+def mask_lanes_route(M: int, N: int, K_fwd: int, K_bwd: int, bwd_wt: bool) -> bool:
+    """True when a ``linear_fwd(..., mask_lanes=True)`` of [M, K_fwd] x [N, K_fwd]^T and the
+    ``linear_dgrad(..., bits_lanes=True)`` of [M, K_bwd] x [K_bwd, N] that reads its mask would
+    BOTH run the lane-private mode under the current kernel choice (``bwd_wt``: the input
+    gradient is given ``Wt``). A caller that keeps a mask across the two calls asks this once and
+    passes the same answer to both."""
+    from ._ext import native
+
+    return native().gemm_mask_lanes_route(int(M), int(N), int(K_fwd), int(K_bwd),
+                                          bool(bwd_wt)) == LANES_OK
+
+
 def linear_fwd(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor | None, out: torch.Tensor,
-               relu: bool = False, mask_out: torch.Tensor | None = None) -> torch.Tensor:
+               relu: bool = False, mask_out: torch.Tensor | None = None,
+               mask_lanes: bool = False) -> torch.Tensor:
     """``mask_out`` (MFMA path, ReLU layers): also write the bitmask 1(out > 0) as uint8
     [M, N/8] (bit e of byte j <-> column 8j+e) for :func:`linear_dgrad`'s ``relu_bits`` -
-    1/16 of the bytes of re-reading the bf16 activation in the backward. Ignored elsewhere."""
+    1/16 of the bytes of re-reading the bf16 activation in the backward. Ignored elsewhere.
+
+    ``mask_lanes``: write the same bytes in the 256x256 kernel's lane-private order instead
+    (``csrc/include/gemm_tile.h``; only ``linear_dgrad(..., bits_lanes=True)`` can read them).
+    Defined for M % 256 == 0 and N % 256 == 0: other shapes write the row-major mask, exactly
+    as the reading side falls back for them. A shape that fits but routes to the 128x128
+    kernel raises (ask :func:`mask_lanes_route` first). ``out`` is the same either way."""
     if _mfma_ok(x, W):
         from ._ext import native
 
+        if mask_lanes and relu and mask_out is not None:
+            rc = native().gemm_nt(x, W, b, out, 1, mask_out, True)
+            if rc == LANES_OK:
+                return out
+            if rc != LANES_SHAPE:
+                raise RuntimeError("linear_fwd: lane-private mask asked for on a product that "
+                                   "runs the 128x128 kernel (see ops.gemm.mask_lanes_route)")
         native().gemm_nt(x, W, b, out, 1 if relu else 0, mask_out if relu else None)
         return out
     if b is not None:
@@ -81,14 +110,23 @@ def linear_fwd(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor | None, out: to
 def linear_dgrad(dy: torch.Tensor, W: torch.Tensor, out: torch.Tensor,
                  relu_of: torch.Tensor | None = None, accumulate: bool = False,
                  relu_bits: torch.Tensor | None = None,
-                 Wt: torch.Tensor | None = None) -> torch.Tensor:
+                 Wt: torch.Tensor | None = None, bits_lanes: bool = False) -> torch.Tensor:
     """out (+)= (dy @ W) * 1(relu_of > 0). ``out`` may be fp32 while dy/W are bf16.
     ``relu_bits`` (MFMA path): the bitmask :func:`linear_fwd` wrote for ``relu_of``, read
     instead of the bf16 activation; the other paths use ``relu_of``. ``Wt`` (MFMA path, bf16
-    output): a current copy of W^T, which runs the product as NT (both operands k-major)."""
+    output): a current copy of W^T, which runs the product as NT (both operands k-major).
+    ``bits_lanes``: ``relu_bits`` came from ``linear_fwd(..., mask_lanes=True)``; shapes the lane
+    layout is not defined for read it row-major (what that call wrote for them)."""
     if _mfma_ok(dy, W):
         from ._ext import native
 
+        if relu_bits is not None and bits_lanes:
+            rc = native().gemm_nn(dy, W, None, out, bool(accumulate), relu_bits, Wt, True)
+            if rc == LANES_OK:
+                return out
+            if rc != LANES_SHAPE:
+                raise RuntimeError("linear_dgrad: lane-private bits on a product that runs the "
+                                   "128x128 kernel (see ops.gemm.mask_lanes_route)")
         if relu_bits is not None:
             native().gemm_nn(dy, W, None, out, bool(accumulate), relu_bits, Wt)
         else:

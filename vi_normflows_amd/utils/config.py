@@ -176,6 +176,7 @@ class KernelPaths:
     cpl_fuse: bool = True        # coupling backward fused into the conditioner's input gradient
     cpl_fwd_fuse: bool = True    # coupling forward fused into the conditioner's last product
     cpl_xbf16: bool = True       # fused coupling backward reads x as its bf16 operand copy
+    relu_mask_lanes: bool = True  # conditioner ReLU bitmasks in the 256x256 kernel's lane order
     wgrad_stream: bool = False   # per-layer weight gradients on a side stream (DP tests)
     maf_fuse: bool = True        # MAF transform fused into the MADE GEMM epilogues
     fp8_dgrad: bool = True       # MAF fp8: e4m3 input gradients
