@@ -76,6 +76,19 @@ void nf_launch_stein_ksd(const float* x, long ldx, const float* score, long lds,
                          const float* h_dev, float h_host, int kind, int S, float* rows,
                          float* diag, float* work, int N, int D, hipStream_t stream);
 
+// glm.hip: log-density and score of B parameter rows of a generalised linear model against N
+// data rows, fp32, 1 <= D <= 64. theta [B, D] / X [N, D] with row strides ldt / ldx in elements
+// and unit inner stride, y [N] dense; family 0 = bernoulli, 1 = poisson, 2 = gaussian (inv_var).
+// The prior precision is prec_dev[D] when not null, else prec_host; has_prior = 0: flat prior.
+// S = nf_glm_splits(B, N, D, n_splits) partial sums per output element go through work
+// ([S, B, D + 1] floats) and are added in fixed order; logp [B], grad [B, D] dense, all written.
+int nf_glm_splits(int B, int N, int D, int n_splits);   // n_splits = 0: chosen from (B, N, D)
+void nf_launch_glm_logp_grad(const float* theta, long ldt, const float* X, long ldx,
+                             const float* y, const float* prec_dev, float prec_host,
+                             int has_prior, int family, float inv_var, float scale, int S,
+                             float* logp, float* grad, float* work, int B, int N, int D,
+                             hipStream_t stream);
+
 // elbo.hip
 void nf_launch_target_logp_grad(int kind, const float* A, long lda, const float* Bh, long ldb,
                                 float* gA, long ldga, float* gB, long ldgb, int grad_accumulate,

@@ -48,6 +48,7 @@ class Target:
     meta: dict = field(default_factory=dict)
     kernel_kind: int | None = None    # csrc/kernels/energy2d.hip kind (2-D reference targets)
     fused: bool = True                # GPU fp32 z -> that kernel (log p and its gradient)
+    score: object | None = None       # z -> grad log p(z) without a graph (inference/svgd.py)
 
     def log_prob(self, z: torch.Tensor) -> torch.Tensor:
         if (self.fused and self.kernel_kind is not None and z.is_cuda
@@ -216,6 +217,10 @@ def get_target(name: str, dim: int | None = None, **kw) -> Target:
     if n == "gaussian":
         d = dim or 784
         return Target("gaussian", d, gaussian(d, **kw), logZ=0.0)
+    if n in ("logreg", "poisreg", "linreg"):   # GLM posteriors on seeded synthetic data
+        from .posteriors import glm_target
+
+        return glm_target(n, dim, **kw)
     raise KeyError(name)
 
 

@@ -23,7 +23,11 @@ from .optimizers import make_optimizer
 
 def score_fn(target: Target):
     """``z -> grad log p(z)`` [N, D] of a target, detached. fp32 GPU samples of a 2-D target with
-    a ``kernel_kind`` take the fused target kernel; everything else autograd on ``target.fn``."""
+    a ``kernel_kind`` take the fused target kernel; everything else autograd on ``target.fn``.
+    A target that brings its own ``score`` (the GLM posteriors) is asked first."""
+    if target.score is not None:
+        return target.score
+
     def score(z):
         z = z.detach()
         if (target.fused and target.kernel_kind is not None and z.is_cuda

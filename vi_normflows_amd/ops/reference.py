@@ -506,3 +506,103 @@ def ksd_rows_reference(x, score, h, kernel: str = "imq", chunk: int = 1024,
         if return_abs:
             B[i0:i1] = (t1.abs() + t2.abs() + t3.abs() + t4.abs()).sum(1)
     return (rows, diag, B) if return_abs else (rows, diag)
+
+
+# ---------------------------------------------------------------------- glm
+GLM_FAMILIES = {"bernoulli": 0, "poisson": 1, "gaussian": 2}
+GLM_CHUNK_ELEMS = 1 << 24   # elements of one [chunk, N] block of the composite
+
+
+def glm_prior_prec(prior_prec, theta):
+    """The prior precision as ``None`` (flat prior) or a ``[D]`` tensor like ``theta``."""
+    if prior_prec is None:
+        return None
+    if isinstance(prior_prec, torch.Tensor):
+        p = prior_prec.detach().to(device=theta.device, dtype=theta.dtype).reshape(-1)
+        if p.numel() == 1:
+            p = p.expand(theta.shape[1])
+        if p.shape[0] != theta.shape[1]:
+            raise ValueError(f"glm: prior_prec has {p.shape[0]} entries, theta has D = "
+                             f"{theta.shape[1]}")
+        return p
+    return torch.full((theta.shape[1],), float(prior_prec), device=theta.device, dtype=theta.dtype)
+
+
+def glm_terms_reference(y, eta, family: str = "bernoulli", noise_var: float = 1.0):
+    """``(ll, r)`` of one GLM family at linear predictor ``eta``, without the terms of ``ll``
+    that are constant in ``eta``: bernoulli ``y eta - softplus(eta)``, ``y - sigmoid(eta)``;
+    poisson ``y eta - exp(eta)``, ``y - exp(eta)``; gaussian ``-(y - eta)^2 / (2 noise_var)``,
+    ``(y - eta) / noise_var``."""
+    if family == "bernoulli":
+        ll = y * eta - eta.clamp_min(0) - torch.log1p(torch.exp(-eta.abs()))
+        return ll, y - torch.sigmoid(eta)
+    if family == "poisson":
+        ex = torch.exp(eta)
+        return y * eta - ex, y - ex
+    if family == "gaussian":
+        d = y - eta
+        return -0.5 * d * d / noise_var, d / noise_var
+    raise ValueError(f"glm: family must be one of {sorted(GLM_FAMILIES)}, got {family!r}")
+
+
+def glm_likelihood_const(y, family: str = "bernoulli", noise_var: float = 1.0) -> float:
+    """The part of ``sum_n log p(y_n | eta_n)`` that does not depend on ``eta``, as a float
+    (fp64): poisson ``-sum lgamma(y + 1)``, gaussian ``-0.5 N log(2 pi noise_var)``, bernoulli 0."""
+    if family == "poisson":
+        return -float(torch.lgamma(y.detach().double() + 1.0).sum())
+    if family == "gaussian":
+        return -0.5 * y.numel() * math.log(2 * math.pi * noise_var)
+    if family == "bernoulli":
+        return 0.0
+    raise ValueError(f"glm: family must be one of {sorted(GLM_FAMILIES)}, got {family!r}")
+
+
+def glm_logp_grad_reference(theta, X, y, family: str = "bernoulli", prior_prec=1.0,
+                            noise_var: float = 1.0, scale: float = 1.0, chunk: int | None = None,
+                            return_abs: bool = False):
+    """``(logp [B], grad [B, D])`` of ``B`` parameter rows of a GLM posterior in the dtype of
+    ``theta``, ``chunk`` rows at a time (memory O(chunk N)):
+
+        logp_i = scale sum_n ll(y_n, theta_i . x_n) + log prior(theta_i)
+        grad_i = scale sum_n r(y_n, theta_i . x_n) x_n - prec theta_i
+
+    with ``ll`` and ``r`` of :func:`glm_terms_reference` and the prior ``N(0, diag(1 / prec))``,
+    ``log prior = -0.5 sum prec_c theta_c^2 + 0.5 sum log prec_c - D/2 log 2 pi`` over the
+    coordinates with ``prec_c > 0`` (``prec_c = 0``: flat in that coordinate; ``prior_prec=None``:
+    no prior at all). ``return_abs=True`` appends ``A_i = scale sum_n |ll_in| + |log prior_i|``
+    and ``G_ic = scale sum_n |r_in x_nc| + |prec_c theta_ic|``: the scales an implementation's
+    rounding error is measured against."""
+    theta = theta.detach()
+    X, y = X.detach().to(theta.dtype), y.detach().to(theta.dtype).reshape(-1)
+    B, D = theta.shape
+    N = X.shape[0]
+    if X.shape[1] != D or y.shape[0] != N:
+        raise ValueError(f"glm: theta {tuple(theta.shape)}, X {tuple(X.shape)} and y "
+                         f"{tuple(y.shape)} do not fit together ([B, D], [N, D], [N])")
+    if not scale > 0 or not noise_var > 0:
+        raise ValueError(f"glm: scale and noise_var must be positive, got {scale} and {noise_var}")
+    prec = glm_prior_prec(prior_prec, theta)
+    chunk = chunk or max(1, GLM_CHUNK_ELEMS // max(N, 1))
+    logp = torch.empty(B, dtype=theta.dtype, device=theta.device)
+    grad = torch.empty_like(theta, memory_format=torch.contiguous_format)
+    A = torch.empty_like(logp) if return_abs else None
+    G = torch.empty_like(grad) if return_abs else None
+    if prec is not None:
+        on = prec > 0
+        cst = 0.5 * torch.log(prec[on]).sum() - 0.5 * int(on.sum()) * math.log(2 * math.pi)
+    Xa = X.abs() if return_abs else None
+    for i0 in range(0, B, chunk):
+        th = theta[i0:i0 + chunk]
+        ll, r = glm_terms_reference(y[None, :], th @ X.T, family, noise_var)
+        lp, g = scale * ll.sum(1), scale * (r @ X)
+        if prec is not None:
+            prior = -0.5 * (prec * th * th).sum(1) + cst
+            lp, g = lp + prior, g - prec * th
+        logp[i0:i0 + chunk], grad[i0:i0 + chunk] = lp, g
+        if return_abs:
+            A[i0:i0 + chunk] = scale * ll.abs().sum(1)
+            G[i0:i0 + chunk] = scale * (r.abs() @ Xa)
+            if prec is not None:
+                A[i0:i0 + chunk] += prior.abs()
+                G[i0:i0 + chunk] += (prec * th).abs()
+    return (logp, grad, A, G) if return_abs else (logp, grad)
