@@ -89,6 +89,23 @@ void nf_launch_glm_logp_grad(const float* theta, long ldt, const float* X, long 
                              float* logp, float* grad, float* work, int B, int N, int D,
                              hipStream_t stream);
 
+// glm_hmc.hip: one HMC trajectory (L leapfrog steps, 1 <= L <= 1024) and its accept step for B
+// chains on a GLM posterior, fp32, 1 <= D <= 64; data, family and prior as for glm.hip. theta0
+// [B, D] with row stride ldt, everything else dense: p0 / grad0 [B, D], logp0 / eps / log_u [B],
+// minv [D] or null (identity mass). Written: theta_prop / p_prop (the trajectory's end),
+// theta_out / logp_out / grad_out (the state after the accept step; bitwise the inputs on a
+// reject), accept (0 or 1) and dH [B]. No output may alias an input. rows = chains per workgroup,
+// one of nf_glm_hmc_rows' values; a chain's result does not depend on it.
+int nf_glm_hmc_rows(int B, int D, int rows);   // rows = 0: chosen from (B, D); -1: not built
+void nf_launch_glm_hmc_trajectory(const float* theta0, long ldt, const float* p0,
+                                  const float* logp0, const float* grad0, const float* eps,
+                                  const float* minv, const float* log_u, int L, const float* X,
+                                  long ldx, const float* y, const float* prec_dev, float prec_host,
+                                  int has_prior, int family, float inv_var, float scale, int rows,
+                                  float* theta_prop, float* p_prop, float* theta_out,
+                                  float* logp_out, float* grad_out, float* accept, float* dH,
+                                  int B, int N, int D, hipStream_t stream);
+
 // elbo.hip
 void nf_launch_target_logp_grad(int kind, const float* A, long lda, const float* Bh, long ldb,
                                 float* gA, long ldga, float* gB, long ldgb, int grad_accumulate,

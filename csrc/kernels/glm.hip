@@ -38,6 +38,7 @@
 // argument error (|eta| 2^-24 relative) is far inside the 1e-4 abs-sum limit of
 // tests/test_glm_gpu.py, which is what decided for the hardware forms over expf / log1pf. The
 // Poisson link overflows as IEEE does (exp(eta) = inf beyond eta ~ 88.7).
+#include "glm_elem.h"
 #include "glm_tiles.h"
 #include "nf_common.h"
 
@@ -45,9 +46,11 @@ namespace nf {
 namespace {
 
 constexpr int TB = NF_GLM_TILE_B;
-constexpr int TN = NF_GLM_TILE_N;
-constexpr int FAM_BERNOULLI = 0, FAM_POISSON = 1, FAM_GAUSSIAN = 2;
-constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
+constexpr int TN = glm::TN;
+using glm::FAM_BERNOULLI;
+using glm::FAM_GAUSSIAN;
+using glm::FAM_POISSON;
+using glm::Link;
 
 struct GlmArgs {
   const float* theta;
@@ -59,62 +62,8 @@ struct GlmArgs {
   int B, N, D, S;
 };
 
-// ll and r of one (y, eta) pair
-template <int FAMILY>
-struct Link;
-
-template <>
-struct Link<FAM_BERNOULLI> {
-  __device__ explicit Link(float) {}
-  __device__ __forceinline__ void eval(float y, float eta, float& ll, float& r) const {
-    const float e = __builtin_amdgcn_exp2f(-fabsf(eta) * LOG2E);   // e^(-|eta|)
-    const float inv = __builtin_amdgcn_rcpf(1.f + e);
-    const float l1p = __builtin_amdgcn_logf(1.f + e) * LN2;        // log1p(e), 1 + e in (1, 2]
-    ll = fmaf(y, eta, -fmaxf(eta, 0.f)) - l1p;
-    r = y - (eta >= 0.f ? inv : e * inv);
-  }
-};
-
-template <>
-struct Link<FAM_POISSON> {
-  __device__ explicit Link(float) {}
-  __device__ __forceinline__ void eval(float y, float eta, float& ll, float& r) const {
-    const float ex = __builtin_amdgcn_exp2f(eta * LOG2E);
-    ll = fmaf(y, eta, -ex);
-    r = y - ex;
-  }
-};
-
-template <>
-struct Link<FAM_GAUSSIAN> {
-  float inv_var;
-  __device__ explicit Link(float iv) : inv_var(iv) {}
-  __device__ __forceinline__ void eval(float y, float eta, float& ll, float& r) const {
-    const float d = y - eta;
-    r = inv_var * d;
-    ll = (-0.5f * r) * d;
-  }
-};
-
-// sum over the LPR adjacent lanes that share a row; every one of them gets the same bits
-template <int LPR>
-__device__ __forceinline__ float part_sum(float v) {
-#pragma unroll
-  for (int off = LPR / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// rows [n0, n0 + TN) of X and y -> tx[n][DP], ty[n]; zero beyond N and beyond D
-template <int DP, int NT>
-__device__ __forceinline__ void stage_tile(const GlmArgs& a, long n0, float* tx, float* ty) {
-  for (int idx = threadIdx.x; idx < TN * DP; idx += NT) {
-    const int n = idx / DP, c = idx % DP;
-    const long gn = n0 + n;
-    tx[idx] = (gn < a.N && c < a.D) ? a.X[gn * a.ldx + c] : 0.f;
-  }
-  for (int n = threadIdx.x; n < TN; n += NT) ty[n] = (n0 + n < a.N) ? a.y[n0 + n] : 0.f;
-}
-
+// The links, the lane sum, the tile staging and the row loop of a tile: glm_elem.h, shared with
+// the trajectory kernel of glm_hmc.hip.
 template <int C, int LPR, int FAMILY>
 __global__ __launch_bounds__(TB* LPR) void glm_pairs_kernel(GlmArgs a) {
   constexpr int DP = C * LPR, NT = TB * LPR;
@@ -139,29 +88,9 @@ __global__ __launch_bounds__(TB* LPR) void glm_pairs_kernel(GlmArgs a) {
     const long n0 = t * TN;
     const int nn = (int)(a.N - n0 < TN ? a.N - n0 : TN);
     __syncthreads();
-    stage_tile<DP, NT>(a, n0, tx, ty);
+    glm::stage_tile<DP, NT>(a.X, a.ldx, a.y, a.N, a.D, n0, tx, ty);
     __syncthreads();
-    float gt[C], lt = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) gt[c] = 0.f;
-    const auto add_row = [&](int n) {
-      const float* xn = tx + n * DP + part * C;
-      float eta = 0.f;
-#pragma unroll
-      for (int c = 0; c < C; ++c) eta = fmaf(th[c], xn[c], eta);
-      eta = part_sum<LPR>(eta);
-      float ll, r;
-      link.eval(ty[n], eta, ll, r);
-      lt += ll;
-#pragma unroll
-      for (int c = 0; c < C; ++c) gt[c] = fmaf(r, xn[c], gt[c]);
-    };
-    // one row per trip: two rows by hand raised the D > 32 instantiations from 94 to 156 VGPRs
-    // and measured 1.45x slower there, no faster elsewhere (docs/PERF_NOTES.md)
-    for (int n = 0; n < nn; ++n) add_row(n);
-    lacc += lt;
-#pragma unroll
-    for (int c = 0; c < C; ++c) acc[c] += gt[c];
+    glm::tile_rows<C, LPR, FAMILY>(link, th, tx, ty, part, nn, acc, lacc);
   }
 
   if (i < a.B) {
@@ -197,26 +126,17 @@ __global__ __launch_bounds__(256) void glm_finalize_kernel(GlmFinalArgs a) {
   const int c = (int)(e % (a.D + 1));
   float sum = 0.f;
   for (int s = 0; s < a.S; ++s) sum += a.work[(long)s * n + e];
-  sum *= a.scale;
+  const glm::Prior pr{a.prec_dev, a.prec_host, a.has_prior};
   const float* th = a.theta + i * a.ldt;
   if (c < a.D) {
-    if (a.has_prior) sum = fmaf(-(a.prec_dev ? a.prec_dev[c] : a.prec_host), th[c], sum);
-    a.grad[i * a.D + c] = sum;
+    a.grad[i * a.D + c] = glm::finish_grad(sum, a.scale, pr, c, th[c]);
   } else {
+    float q = 0.f, cst = 0.f;
     if (a.has_prior) {
-      float q = 0.f, lg = 0.f;
-      int k = 0;
-      for (int d = 0; d < a.D; ++d) {
-        const float p = a.prec_dev ? a.prec_dev[d] : a.prec_host;
-        q = fmaf(p * th[d], th[d], q);
-        if (p > 0.f) {
-          lg += logf(p);
-          ++k;
-        }
-      }
-      sum += fmaf(-0.5f, q, fmaf(0.5f, lg, -0.9189385332046727f * (float)k));
+      for (int d = 0; d < a.D; ++d) q = glm::prior_quad(q, pr.prec(d), th[d]);
+      cst = glm::log_prior_const(pr, a.D);
     }
-    a.logp[i] = sum;
+    a.logp[i] = glm::finish_logp(sum, a.scale, pr, q, cst);
   }
 }
 
