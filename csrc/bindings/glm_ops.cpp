@@ -1,5 +1,6 @@
 // TORCH_LIBRARY fragment for the GLM likelihood kernel (glm.hip): log-density and score of B
-// parameter rows against N data rows. The op is not differentiable; ops/glm.py wraps it in an
+// parameter rows against N data rows, and for the pass that adds the negative Hessian
+// (glm_hess.hip). The ops are not differentiable; ops/glm.py wraps the first in an
 // autograd.Function that hands the score back as the gradient.
 #include <torch/library.h>
 #include <ATen/ATen.h>
@@ -43,10 +44,17 @@ void chk_splits(const char* who, int64_t n_splits) {
               ", got ", n_splits);
 }
 
-void glm_logp_grad(const at::Tensor& theta, const at::Tensor& X, const at::Tensor& y,
-                   const c10::optional<at::Tensor>& prec_dev, double prec_host, bool has_prior,
-                   int64_t family, double inv_var, double scale, int64_t n_splits,
-                   const at::Tensor& logp, const at::Tensor& grad, const at::Tensor& work) {
+// the inputs of a pass, checked
+struct GlmIn {
+  int64_t B, N, D;
+  long ldt, ldx;
+  const float* prec_dev;
+  at::Device dev;
+};
+
+GlmIn chk_inputs(const at::Tensor& theta, const at::Tensor& X, const at::Tensor& y,
+                 const c10::optional<at::Tensor>& prec_dev, double prec_host, bool has_prior,
+                 int64_t family, double inv_var, double scale, int64_t n_splits) {
   TORCH_CHECK(theta.is_cuda(), "glm: theta must be a GPU tensor");
   TORCH_CHECK(theta.dim() == 2, "glm: theta [B, D] expected, got ", theta.dim(), " dimensions");
   const int64_t B = theta.size(0), D = theta.size(1);
@@ -78,15 +86,47 @@ void glm_logp_grad(const at::Tensor& theta, const at::Tensor& X, const at::Tenso
                   "glm: the prior precision must be >= 0, got prec_host = ", prec_host);
     }
   }
+  return GlmIn{B, N, D, ldt, ldx, pd, dev};
+}
+
+void glm_logp_grad(const at::Tensor& theta, const at::Tensor& X, const at::Tensor& y,
+                   const c10::optional<at::Tensor>& prec_dev, double prec_host, bool has_prior,
+                   int64_t family, double inv_var, double scale, int64_t n_splits,
+                   const at::Tensor& logp, const at::Tensor& grad, const at::Tensor& work) {
+  const GlmIn in = chk_inputs(theta, X, y, prec_dev, prec_host, has_prior, family, inv_var, scale,
+                              n_splits);
+  const int64_t B = in.B, N = in.N, D = in.D;
   const int S = nf_glm_splits((int)B, (int)N, (int)D, (int)n_splits);
-  chk_out(logp, "logp", B, true, dev);
-  chk_out(grad, "grad", B * D, true, dev);
-  chk_out(work, "work", (int64_t)S * B * (D + 1), false, dev);
-  nf_launch_glm_logp_grad(theta.data_ptr<float>(), ldt, X.data_ptr<float>(), ldx,
-                          y.data_ptr<float>(), pd, (float)prec_host, has_prior ? 1 : 0,
+  chk_out(logp, "logp", B, true, in.dev);
+  chk_out(grad, "grad", B * D, true, in.dev);
+  chk_out(work, "work", (int64_t)S * B * (D + 1), false, in.dev);
+  nf_launch_glm_logp_grad(theta.data_ptr<float>(), in.ldt, X.data_ptr<float>(), in.ldx,
+                          y.data_ptr<float>(), in.prec_dev, (float)prec_host, has_prior ? 1 : 0,
                           (int)family, (float)inv_var, (float)scale, S, logp.data_ptr<float>(),
                           grad.data_ptr<float>(), work.data_ptr<float>(), (int)B, (int)N, (int)D,
                           cur_stream());
+}
+
+// logp, grad and hess [B, D, D] (the negative Hessian of logp) from one pass of glm_hess.hip
+void glm_logp_grad_hess(const at::Tensor& theta, const at::Tensor& X, const at::Tensor& y,
+                        const c10::optional<at::Tensor>& prec_dev, double prec_host,
+                        bool has_prior, int64_t family, double inv_var, double scale,
+                        int64_t n_splits, const at::Tensor& logp, const at::Tensor& grad,
+                        const at::Tensor& hess, const at::Tensor& work) {
+  const GlmIn in = chk_inputs(theta, X, y, prec_dev, prec_host, has_prior, family, inv_var, scale,
+                              n_splits);
+  const int64_t B = in.B, N = in.N, D = in.D;
+  const int S = nf_glm_hess_splits((int)B, (int)N, (int)D, (int)n_splits);
+  chk_out(logp, "logp", B, true, in.dev);
+  chk_out(grad, "grad", B * D, true, in.dev);
+  chk_out(hess, "hess", B * D * D, true, in.dev);
+  chk_out(work, "work", (int64_t)S * B * (D * D + D + 1), false, in.dev);
+  nf_launch_glm_logp_grad_hess(theta.data_ptr<float>(), in.ldt, X.data_ptr<float>(), in.ldx,
+                               y.data_ptr<float>(), in.prec_dev, (float)prec_host,
+                               has_prior ? 1 : 0, (int)family, (float)inv_var, (float)scale, S,
+                               logp.data_ptr<float>(), grad.data_ptr<float>(),
+                               hess.data_ptr<float>(), work.data_ptr<float>(), (int)B, (int)N,
+                               (int)D, cur_stream());
 }
 
 // floats of workspace: [S, B, D + 1]
@@ -97,6 +137,14 @@ int64_t glm_workspace(int64_t B, int64_t N, int64_t D, int64_t n_splits) {
   return (int64_t)nf_glm_splits((int)B, (int)N, (int)D, (int)n_splits) * B * (D + 1);
 }
 
+// floats of workspace: [S, B, D D + D + 1]
+int64_t glm_hess_workspace(int64_t B, int64_t N, int64_t D, int64_t n_splits) {
+  TORCH_CHECK(B >= 1 && B < kMaxRows && N >= 1 && N < kMaxRows && D >= 1 && D <= kMaxDim,
+              "glm_hess_workspace: need 1 <= B, N < 2^31 and 1 <= D <= ", kMaxDim);
+  chk_splits("glm_hess_workspace", n_splits);
+  return (int64_t)nf_glm_hess_splits((int)B, (int)N, (int)D, (int)n_splits) * B * (D * D + D + 1);
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(vinf, m) {
@@ -104,8 +152,13 @@ TORCH_LIBRARY_FRAGMENT(vinf, m) {
         "bool has_prior, int family, float inv_var, float scale, int n_splits, "
         "Tensor(a!) logp, Tensor(b!) grad, Tensor(c!) work) -> ()");
   m.def("glm_workspace(int B, int N, int D, int n_splits) -> int", &glm_workspace);
+  m.def("glm_logp_grad_hess(Tensor theta, Tensor X, Tensor y, Tensor? prec_dev, float prec_host, "
+        "bool has_prior, int family, float inv_var, float scale, int n_splits, "
+        "Tensor(a!) logp, Tensor(b!) grad, Tensor(c!) hess, Tensor(d!) work) -> ()");
+  m.def("glm_hess_workspace(int B, int N, int D, int n_splits) -> int", &glm_hess_workspace);
 }
 
 TORCH_LIBRARY_IMPL(vinf, CUDA, m) {
   m.impl("glm_logp_grad", &glm_logp_grad);
+  m.impl("glm_logp_grad_hess", &glm_logp_grad_hess);
 }

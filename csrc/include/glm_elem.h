@@ -1,5 +1,5 @@
 // Device-side pieces shared by the GLM kernels (glm.hip: one log-density / score pass;
-// glm_hmc.hip: a whole leapfrog trajectory of such passes): the links of the three families, the
+// glm_hmc.hip: a whole leapfrog trajectory of such passes; glm_hess.hip: a pass with curvature): the links of the three families, the
 // sum over the lanes that share a parameter row, the staging of a data tile in LDS, the row loop
 // of one tile and the prior / scale step that turns the summed partials into log p and the score.
 // Both kernels go through the same functions, so a pass inside a trajectory has the bits of the
@@ -18,7 +18,8 @@ constexpr int FAM_BERNOULLI = 0, FAM_POISSON = 1, FAM_GAUSSIAN = 2;
 constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 constexpr float HALF_LOG_2PI = 0.9189385332046727f;
 
-// ll and r of one (y, eta) pair
+// ll and r of one (y, eta) pair; eval_w adds the weight w = -d r / d eta of the Hessian
+// (glm_hess.hip)
 template <int FAMILY>
 struct Link;
 
@@ -32,6 +33,16 @@ struct Link<FAM_BERNOULLI> {
     ll = fmaf(y, eta, -fmaxf(eta, 0.f)) - l1p;
     r = y - (eta >= 0.f ? inv : e * inv);
   }
+  // eval and the weight w = sigmoid(eta) (1 - sigmoid(eta)) = e / (1 + e)^2 from the same e and
+  // inv: it underflows to 0 at large |eta|, nothing overflows
+  __device__ __forceinline__ void eval_w(float y, float eta, float& ll, float& r, float& w) const {
+    const float e = __builtin_amdgcn_exp2f(-fabsf(eta) * LOG2E);
+    const float inv = __builtin_amdgcn_rcpf(1.f + e);
+    const float l1p = __builtin_amdgcn_logf(1.f + e) * LN2;
+    ll = fmaf(y, eta, -fmaxf(eta, 0.f)) - l1p;
+    r = y - (eta >= 0.f ? inv : e * inv);
+    w = e * inv * inv;
+  }
 };
 
 template <>
@@ -41,6 +52,13 @@ struct Link<FAM_POISSON> {
     const float ex = __builtin_amdgcn_exp2f(eta * LOG2E);
     ll = fmaf(y, eta, -ex);
     r = y - ex;
+  }
+  // eval and the weight w = exp(eta) (IEEE overflow, as r)
+  __device__ __forceinline__ void eval_w(float y, float eta, float& ll, float& r, float& w) const {
+    const float ex = __builtin_amdgcn_exp2f(eta * LOG2E);
+    ll = fmaf(y, eta, -ex);
+    r = y - ex;
+    w = ex;
   }
 };
 
@@ -52,6 +70,11 @@ struct Link<FAM_GAUSSIAN> {
     const float d = y - eta;
     r = inv_var * d;
     ll = (-0.5f * r) * d;
+  }
+  // eval and the constant weight w = inv_var
+  __device__ __forceinline__ void eval_w(float y, float eta, float& ll, float& r, float& w) const {
+    eval(y, eta, ll, r);
+    w = inv_var;
   }
 };
 

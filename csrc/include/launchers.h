@@ -89,6 +89,17 @@ void nf_launch_glm_logp_grad(const float* theta, long ldt, const float* X, long 
                              float* logp, float* grad, float* work, int B, int N, int D,
                              hipStream_t stream);
 
+// glm_hess.hip: the Newton statistics of the same posteriors in one pass: logp [B], grad [B, D]
+// and hess [B, D, D] = scale sum_n w(eta_bn) x_n x_n^T + diag(prec), the negative Hessian of
+// logp, exactly symmetric. Arguments as for glm.hip; S = nf_glm_hess_splits(B, N, D, n_splits)
+// partial sums go through work ([S, B, D D + D + 1] floats) and are added in fixed order.
+int nf_glm_hess_splits(int B, int N, int D, int n_splits);   // n_splits = 0: chosen from (B, N, D)
+void nf_launch_glm_logp_grad_hess(const float* theta, long ldt, const float* X, long ldx,
+                                  const float* y, const float* prec_dev, float prec_host,
+                                  int has_prior, int family, float inv_var, float scale, int S,
+                                  float* logp, float* grad, float* hess, float* work, int B, int N,
+                                  int D, hipStream_t stream);
+
 // glm_hmc.hip: one HMC trajectory (L leapfrog steps, 1 <= L <= 1024) and its accept step for B
 // chains on a GLM posterior, fp32, 1 <= D <= 64; data, family and prior as for glm.hip. theta0
 // [B, D] with row stride ldt, everything else dense: p0 / grad0 [B, D], logp0 / eps / log_u [B],

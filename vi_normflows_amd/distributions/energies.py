@@ -49,6 +49,8 @@ class Target:
     kernel_kind: int | None = None    # csrc/kernels/energy2d.hip kind (2-D reference targets)
     fused: bool = True                # GPU fp32 z -> that kernel (log p and its gradient)
     score: object | None = None       # z -> grad log p(z) without a graph (inference/svgd.py)
+    hessian: object | None = None     # z -> (log p, grad, -Hessian) [B], [B, D], [B, D, D]
+                                      # without a graph (inference/laplace.py)
 
     def log_prob(self, z: torch.Tensor) -> torch.Tensor:
         if (self.fused and self.kernel_kind is not None and z.is_cuda

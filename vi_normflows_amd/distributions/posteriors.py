@@ -86,6 +86,14 @@ class GLMData:
         return glm.glm_logp_grad(z.detach(), X, y, self.family, prec, self.noise_var,
                                  impl=self.impl)[1]
 
+    def hessian(self, z):
+        """The Newton statistics ``(logp [B], grad [B, D], H [B, D, D])`` at ``z`` from one pass
+        over the data, detached: ``logp`` with the likelihood constants, ``H`` the negative
+        Hessian of ``logp`` (``ops/glm.py`` ``glm_logp_grad_hess``)."""
+        X, y, prec = self.on(z)
+        return glm.glm_logp_grad_hess(z.detach(), X, y, self.family, prec, self.noise_var,
+                                      impl=self.impl, const=self.const)
+
 
 def bayes_glm(X, y, family: str = "bernoulli", prior_var=1.0, noise_var: float = 1.0,
               name: str | None = None, impl: str = "auto") -> Target:
@@ -95,7 +103,7 @@ def bayes_glm(X, y, family: str = "bernoulli", prior_var=1.0, noise_var: float =
     it later)."""
     data = GLMData(X, y, family, prior_var, noise_var, impl)
     return Target(name or f"glm_{family}", data.X.shape[1], data.log_prob, logZ=None,
-                  meta={"glm": data}, score=data.score)
+                  meta={"glm": data}, score=data.score, hessian=data.hessian)
 
 
 def minibatch_log_prob(target: Target, idx):

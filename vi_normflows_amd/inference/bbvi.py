@@ -75,11 +75,14 @@ class FullRankBBVIResult:
 
 def black_box_vi_full_rank(logprob, D: int, num_samples: int = 1000, iters: int = 1000,
                            lr: float = 0.1, seed: int = 0, init_mean=None, init_log_std=None,
-                           log_every: int = 100, callback=None) -> FullRankBBVIResult:
+                           log_every: int = 100, callback=None, init=None) -> FullRankBBVIResult:
     """Maximise E_q[log p(w)] + H[q] for the full-rank q = N(mean, L L^T) (full-rank ADVI,
     Kucukelbir et al. 2017): ``L`` lower triangular with a free strict lower triangle and
     ``diag(L) = 1e-3 + softplus(raw_diag)``, starting at ``diag(exp(init_log_std))``. Same
-    arguments and fp64 Adam loop as :func:`black_box_vi`; ``callback(t, lower, mean, scale_tril)``."""
+    arguments and fp64 Adam loop as :func:`black_box_vi`; ``callback(t, lower, mean, scale_tril)``.
+    ``init`` starts q at a given Gaussian instead: anything with ``mean`` [D] and ``scale_tril``
+    [D, D] (a ``FullRankNormal``, a ``LaplaceResult``); ``init_mean`` / ``init_log_std`` must then
+    be left alone."""
     from ..flows.linear import DIAG_FLOOR, positive_diag
 
     g = torch.Generator().manual_seed(seed)
@@ -89,6 +92,21 @@ def black_box_vi_full_rank(logprob, D: int, num_samples: int = 1000, iters: int 
         torch.exp(torch.as_tensor(init_log_std, dtype=torch.float64))
     raw_diag = torch.log(torch.expm1((std0 - DIAG_FLOOR).clamp_min(1e-6)))
     lower = torch.zeros(D, D, dtype=torch.float64)
+    if init is not None:
+        if init_mean is not None or init_log_std is not None:
+            raise ValueError("black_box_vi_full_rank: give init or init_mean / init_log_std, "
+                             "not both")
+        mean = torch.as_tensor(init.mean).detach().double().cpu().reshape(-1).clone()
+        L0 = torch.as_tensor(init.scale_tril).detach().double().cpu()
+        if mean.shape != (D,) or L0.shape != (D, D):
+            raise ValueError(f"black_box_vi_full_rank: init must have mean [{D}] and scale_tril "
+                             f"[{D}, {D}], got {tuple(mean.shape)} and {tuple(L0.shape)}")
+        d0 = torch.diagonal(L0)
+        if not bool((d0 > DIAG_FLOOR).all()):
+            raise ValueError(f"black_box_vi_full_rank: init.scale_tril needs a diagonal above "
+                             f"{DIAG_FLOOR}, got a minimum of {float(d0.min()):.3g}")
+        raw_diag = torch.log(torch.expm1(d0 - DIAG_FLOOR))
+        lower = torch.tril(L0, -1).clone()
     for p in (mean, lower, raw_diag):
         p.requires_grad_(True)
     opt = torch.optim.Adam([mean, lower, raw_diag], lr=lr)

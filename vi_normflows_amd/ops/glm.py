@@ -19,6 +19,10 @@ row-offset minibatches), and the partial sums of ``n_splits`` ranges of data row
 fixed order, so a result is bitwise repeatable for a given ``(B, N, D, n_splits)``;
 ``n_splits=None`` lets the launcher choose from ``(B, N, D)`` alone.
 
+:func:`glm_logp_grad_hess` adds the curvature in the same pass: ``H_i = scale sum_n w(eta_in) x_n
+x_n^T + diag(prec)``, the negative Hessian of ``logp_i`` (``csrc/kernels/glm_hess.hip``), what
+Newton's method and the Laplace approximation of ``inference/laplace.py`` need.
+
 :func:`glm_logp_grad` runs without grad. :func:`glm_log_prob` is differentiable in ``theta`` (once):
 its backward is ``g[:, None] * grad`` from the same launch.
 """
@@ -161,3 +165,44 @@ def glm_log_prob(theta, X, y, family: str = "bernoulli", prior_prec=1.0, noise_v
                                "grad (detach it)")
     return _GlmLogProb.apply(theta, X, y, family, prior_prec, noise_var, scale, impl, n_splits,
                              const)
+
+
+@torch.no_grad()
+def glm_logp_grad_hess(theta, X, y, family: str = "bernoulli", prior_prec=1.0,
+                       noise_var: float = 1.0, scale: float = 1.0, impl: str = "auto",
+                       n_splits=None, const: float = 0.0):
+    """The Newton statistics ``(logp [B], grad [B, D], H [B, D, D])`` of the parameter rows
+    ``theta`` on data ``X`` [N, D], ``y`` [N] from one pass over the data; no-grad. ``H_b = scale
+    sum_n w(theta_b . x_n) x_n x_n^T + diag(prior_prec)`` is the negative Hessian of ``logp_b``
+    (``w``: ``ops/reference.py`` ``glm_weights_reference``). fp32 GPU tensors with D <= 64 run
+    ``csrc/kernels/glm_hess.hip`` (``H`` exactly symmetric, bitwise repeatable for a given ``(B,
+    N, D, n_splits)``, strided views as for :func:`glm_logp_grad`); ``impl`` and ``const`` as
+    there. A kernel launch counts in :func:`glm_launches`."""
+    global _glm_launches
+    # auto: the kernel wherever it is supported; bench/glm_hess_bench.py against the composite is
+    # in docs/PERF_NOTES.md "GLM Hessian"
+    if not _check(theta, X, y, family, prior_prec, noise_var, scale, impl):
+        logp, grad, H = reference.glm_hessian_reference(theta, X, y, family, prior_prec,
+                                                        noise_var, float(scale))
+        return (logp + const if const else logp), grad, H
+    theta, X, y = _rows(theta.detach()), _rows(X.detach()), y.detach().contiguous()
+    B, D = theta.shape
+    N = X.shape[0]
+    prec_dev, prec_host = None, 0.0
+    if isinstance(prior_prec, torch.Tensor):
+        prec_dev = reference.glm_prior_prec(prior_prec, theta).contiguous()
+    elif prior_prec is not None:
+        prec_host = float(prior_prec)
+    ops, ns = native(), int(n_splits or 0)
+    logp = torch.empty(B, device=theta.device, dtype=torch.float32)
+    grad = torch.empty(B, D, device=theta.device, dtype=torch.float32)
+    H = torch.empty(B, D, D, device=theta.device, dtype=torch.float32)
+    work = torch.empty(ops.glm_hess_workspace(B, N, D, ns), device=theta.device,
+                       dtype=torch.float32)
+    ops.glm_logp_grad_hess(theta, X, y, prec_dev, prec_host, prior_prec is not None,
+                           GLM_FAMILIES[family], 1.0 / float(noise_var), float(scale), ns, logp,
+                           grad, H, work)
+    _glm_launches += 1
+    if const:
+        logp += const
+    return logp, grad, H

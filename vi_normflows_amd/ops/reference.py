@@ -606,3 +606,53 @@ def glm_logp_grad_reference(theta, X, y, family: str = "bernoulli", prior_prec=1
                 A[i0:i0 + chunk] += prior.abs()
                 G[i0:i0 + chunk] += (prec * th).abs()
     return (logp, grad, A, G) if return_abs else (logp, grad)
+
+
+def glm_weights_reference(eta, family: str = "bernoulli", noise_var: float = 1.0):
+    """``w = -d r / d eta`` of one GLM family, the weight of a data row in the negative Hessian:
+    bernoulli ``sigmoid(eta) (1 - sigmoid(eta))`` (as ``e / (1 + e)^2`` with ``e = exp(-|eta|)``,
+    which only underflows), poisson ``exp(eta)``, gaussian ``1 / noise_var``."""
+    if family == "bernoulli":
+        e = torch.exp(-eta.abs())
+        return e / ((1 + e) * (1 + e))
+    if family == "poisson":
+        return torch.exp(eta)
+    if family == "gaussian":
+        return torch.full_like(eta, 1.0 / noise_var)
+    raise ValueError(f"glm: family must be one of {sorted(GLM_FAMILIES)}, got {family!r}")
+
+
+def glm_hessian_reference(theta, X, y, family: str = "bernoulli", prior_prec=1.0,
+                          noise_var: float = 1.0, scale: float = 1.0, return_abs: bool = False,
+                          chunk: int | None = None):
+    """``(logp [B], grad [B, D], H [B, D, D])`` of ``B`` parameter rows of a GLM posterior in the
+    dtype of ``theta``: ``logp`` and ``grad`` of :func:`glm_logp_grad_reference` and the negative
+    Hessian of ``logp``
+
+        H_b = scale sum_n w(theta_b . x_n) x_n x_n^T + diag(prec)
+
+    with ``w`` of :func:`glm_weights_reference`, ``chunk`` rows at a time so that the ``[chunk,
+    N, D]`` block of weighted data stays within ``GLM_CHUNK_ELEMS``. ``return_abs=True`` appends
+    ``A``, ``G`` (of :func:`glm_logp_grad_reference`) and ``W_bjk = scale sum_n |w x_nj x_nk| +
+    prec_j delta_jk``."""
+    out = glm_logp_grad_reference(theta, X, y, family, prior_prec, noise_var, scale,
+                                  return_abs=return_abs)
+    theta = theta.detach()
+    X = X.detach().to(theta.dtype)
+    B, D = theta.shape
+    N = X.shape[0]
+    prec = glm_prior_prec(prior_prec, theta)
+    chunk = chunk or max(1, GLM_CHUNK_ELEMS // max(N * D, 1))
+    H = torch.empty(B, D, D, dtype=theta.dtype, device=theta.device)
+    W = torch.empty_like(H) if return_abs else None
+    Xa = X.abs() if return_abs else None
+    for i0 in range(0, B, chunk):
+        w = glm_weights_reference(theta[i0:i0 + chunk] @ X.T, family, noise_var)
+        H[i0:i0 + chunk] = scale * ((w[:, :, None] * X).mT @ X)
+        if return_abs:
+            W[i0:i0 + chunk] = scale * ((w.abs()[:, :, None] * Xa).mT @ Xa)
+    if prec is not None:
+        H.diagonal(dim1=1, dim2=2).add_(prec)
+        if return_abs:
+            W.diagonal(dim1=1, dim2=2).add_(prec.abs())
+    return (out[0], out[1], H, out[2], out[3], W) if return_abs else (out[0], out[1], H)
