@@ -252,9 +252,8 @@ __device__ __forceinline__ void epi_store(const GemmArgs& a, v4f v, int m, int n
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] = relu_f(v[r]);
     }
-    ushort4 o;
-    o.x = f2bf(v[0]); o.y = f2bf(v[1]); o.z = f2bf(v[2]); o.w = f2bf(v[3]);
-    *reinterpret_cast<ushort4*>((bf16_t*)a.C + (long)m * a.ldc + n) = o;
+    *reinterpret_cast<uint2*>((bf16_t*)a.C + (long)m * a.ldc + n) =
+        make_uint2(f2bf_pk(v[0], v[1]), f2bf_pk(v[2], v[3]));
   } else if (EPI == EPI_BF16_RELUMASK) {
     if (a.aux_bits) {
       const unsigned b = ((const unsigned char*)a.aux)[(long)m * a.ld_aux + (n >> 3)] >> (n & 4);
@@ -268,9 +267,8 @@ __device__ __forceinline__ void epi_store(const GemmArgs& a, v4f v, int m, int n
       v[2] = (h.z != 0 && !(h.z & 0x8000)) ? v[2] : 0.f;
       v[3] = (h.w != 0 && !(h.w & 0x8000)) ? v[3] : 0.f;
     }
-    ushort4 o;
-    o.x = f2bf(v[0]); o.y = f2bf(v[1]); o.z = f2bf(v[2]); o.w = f2bf(v[3]);
-    *reinterpret_cast<ushort4*>((bf16_t*)a.C + (long)m * a.ldc + n) = o;
+    *reinterpret_cast<uint2*>((bf16_t*)a.C + (long)m * a.ldc + n) =
+        make_uint2(f2bf_pk(v[0], v[1]), f2bf_pk(v[2], v[3]));
   } else if (EPI == EPI_F32) {
     if (a.cmask) {
       const uchar4 mk = *reinterpret_cast<const uchar4*>(a.cmask + (long)m * a.N + n);
@@ -330,10 +328,114 @@ __device__ __forceinline__ unsigned lane_mask_keep(unsigned w, int i, int j, int
   const int bit = (r == 0 ? 15 : r == 1 ? 31 : r == 2 ? 7 : 23) - s;
   return (unsigned)((int)(w << (31 - bit)) >> 31);
 }
+// acc & keep as one v_and_b32 the compiler cannot see through: written in C++, the and of a
+// float's bits with lane_mask_keep's all-ones / zero becomes a bit test, a compare and a select,
+// three VALU ops per accumulator where v_bfe_i32 + v_and_b32 are two
+__device__ __forceinline__ float lane_mask_apply(float v, unsigned keep) {
+  float r;
+  asm("v_and_b32 %0, %1, %2" : "=v"(r) : "v"(v), "v"(keep));
+  return r;
+}
+// Both halves of a packed bf16 word at once: 1 in a half iff that bf16 is > 0, i.e. iff the half
+// read as a signed 16-bit integer is in [1, 0x7fff] - what bf_pos_pair marks with bit 15 / 31
+// (bf_pos01_pair(w) == bf_pos_pair(w) >> 15 for every w; tests/test_gemm_epilogue_host.py).
+// Signed max with 0 clears the halves with the sign bit set, signed min with 1 turns every
+// remaining non-zero half into 1: two packed VALU ops where bf_pos_pair takes four. (As plain
+// C++ the compiler turns the clamp into two compares and two selects per word.)
+__device__ __forceinline__ unsigned bf_pos01_pair(unsigned w) {
+  unsigned t, r;
+  asm("v_pk_max_i16 %0, %1, 0" : "=v"(t) : "v"(w));
+  asm("v_pk_min_i16 %0, %1, %2" : "=v"(r) : "v"(t), "s"(0x00010001u));
+  return r;
+}
 // Host side: the shapes / alignment the lane-private layout is defined for.
 inline bool lanes_ok(const GemmArgs& a, const void* mask) {
   return a.M > 0 && a.N > 0 && a.M % 256 == 0 && a.N % 256 == 0 && mask != nullptr &&
          ((unsigned long)mask & 15) == 0 && !a.krange && !a.skip;
+}
+
+// The staged bf16 epilogue of the lane-private products (epi_tile_staged with LANES; its
+// parameters). lanes_ok() guarantees whole 256x256 tiles and bf16 operands, and the forward's
+// launcher requires ReLU, so this is one straight line: no bounds predicates, no ReLU flag, no
+// e4m3 factors. These epilogues run with the MFMA pipe idle and are bound by VALU issue, so the
+// addresses are built once per call instead of per access:
+//   staging writes  row j*16 + c, slot i*4 + g: bf_stage_off(row, slot) = bf_stage_off(c, slot)
+//                   + j * 2 KiB (row & 7 = c & 7, row bit 3 = c bit 3) - four lane values, the j
+//                   term in the ds_write's immediate offset;
+//   readback        row it*8 + (lane >> 3): one lane value + it * 1 KiB;
+//   C stores        one pointer per lane, advanced by 8 rows per store.
+// EPI_BF16: y = relu(acc + bias) and the lane's mask bits, from the packed words as staged;
+// EPI_BF16_RELUMASK: y = acc where the lane's bit (lb) is set, +0 elsewhere. Values and bytes
+// are those of the general path.
+template <int EPI, int NJ, int J0, int NJA>
+__device__ __forceinline__ void epi_tile_lanes(const GemmArgs& a, const v4f (&acc)[4][NJA],
+                                               int m0, int n0, char* region, int lane, v4u lb) {
+  constexpr bool OUT = EPI == EPI_BF16;
+  const int g = lane >> 4, c = lane & 15;
+  LDS_AS char* rl = (LDS_AS char*)region;
+  float bv[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bv[i][r] = 0.f;
+  if (OUT && a.bias) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const ushort4 bb = *reinterpret_cast<const ushort4*>(a.bias + n0 + i * 16 + g * 4);
+      bv[i][0] = bf2f(bb.x); bv[i][1] = bf2f(bb.y); bv[i][2] = bf2f(bb.z); bv[i][3] = bf2f(bb.w);
+    }
+  }
+  int wo[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) wo[i] = bf_stage_off(c, i * 4 + g);
+  unsigned mw[NJ / 2];   // OUT: this call's dwords of the lane's mask
+#pragma unroll
+  for (int d = 0; d < NJ / 2; ++d) mw[d] = 0u;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float v0 = acc[i][J0 + j][0], v1 = acc[i][J0 + j][1];
+      float v2 = acc[i][J0 + j][2], v3 = acc[i][J0 + j][3];
+      if constexpr (!OUT) {   // masked accumulators become +0, which stores as bf16 +0
+        const unsigned w = lb[((J0 + j) >> 2) * 2 + (i >> 1)];
+        v0 = lane_mask_apply(v0, lane_mask_keep(w, i, J0 + j, 0));
+        v1 = lane_mask_apply(v1, lane_mask_keep(w, i, J0 + j, 1));
+        v2 = lane_mask_apply(v2, lane_mask_keep(w, i, J0 + j, 2));
+        v3 = lane_mask_apply(v3, lane_mask_keep(w, i, J0 + j, 3));
+      }
+      // (+ 0 on the masked product too: it is what turns a -0 accumulator into the stored +0;
+      // on float pairs, so that the adds stay v_pk_add_f32)
+      typedef float v2f_ __attribute__((ext_vector_type(2)));
+      const v2f_ s01 = (v2f_){v0, v1} + (v2f_){bv[i][0], bv[i][1]};
+      const v2f_ s23 = (v2f_){v2, v3} + (v2f_){bv[i][2], bv[i][3]};
+      v0 = s01[0]; v1 = s01[1]; v2 = s23[0]; v3 = s23[1];
+      if constexpr (OUT) { v0 = relu_f(v0); v1 = relu_f(v1); v2 = relu_f(v2); v3 = relu_f(v3); }
+      const unsigned lo = f2bf_pk(v0, v1), hi = f2bf_pk(v2, v3);
+      if constexpr (OUT) {
+        // bytes 1 / 3 of the dword take lo's halves and bytes 0 / 2 hi's, each at bit 7 - s
+        const int s = (i & 1) * 4 + ((J0 + j) & 3);
+        mw[(j >> 2) * 2 + (i >> 1)] |= ((bf_pos01_pair(lo) << 8) | bf_pos01_pair(hi)) << (7 - s);
+      }
+      *(LDS_AS v2u*)(rl + wo[i] + j * 2048) = (v2u){lo, hi};
+    }
+  }
+  if constexpr (OUT) {   // one coalesced store per lane: no cross-lane work, no byte stores
+    unsigned char* mp = a.mask_out + lane_mask_off(a.N, m0, n0, lane) + (J0 >> 2) * 8;
+    if constexpr (NJ == 8) *reinterpret_cast<v4u*>(mp) = (v4u){mw[0], mw[1], mw[2], mw[3]};
+    else *reinterpret_cast<v2u*>(mp) = (v2u){mw[0], mw[1]};
+  }
+  const int q = lane & 7, r8 = lane >> 3;
+  const LDS_AS char* rp = rl + r8 * 128 + ((q ^ r8) << 4);
+  bf16_t* cp = (bf16_t*)a.C + (long)(m0 + r8) * a.ldc + (n0 + q * 8);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int it = 0; it < NJ * 2; ++it) {
+    // row bit 3 == it & 1: the half swap of bf_stage_off is a compile-time register swap
+    const v4u v = bf_stage_fix(*(const LDS_AS v4u*)(rp + it * 1024), (it & 1) != 0);
+    *reinterpret_cast<uint4*>(cp) = make_uint4(v[0], v[1], v[2], v[3]);
+    cp += 8 * a.ldc;
+  }
 }
 
 // LDS-staged epilogue. In the fragment layout one store instruction covers 16 rows x 32 B
@@ -351,10 +453,10 @@ inline bool lanes_ok(const GemmArgs& a, const void* mask) {
 // J0 / NJA: the rows handled are accumulator blocks [J0, J0 + NJ) of a [4][NJA] array (m0 is the
 // origin of block J0), so a caller short of LDS can stage a sub-tile in several calls.
 // LANES (gemm256 only, bf16 operands, full 256x256 tiles): the ReLU mask in the lane-private
-// layout above. EPI_BF16: the bits come from the packed words as they are staged and leave in
-// one 8- or 16-byte store per lane; EPI_BF16_RELUMASK: `lb` holds the lane's 16 mask bytes
-// (loaded by the caller) and is applied to the accumulators as they are staged. Either way the
-// readback loop only writes C.
+// layout above, by epi_tile_lanes. EPI_BF16: the bits come from the packed words as they are
+// staged and leave in one 8- or 16-byte store per lane; EPI_BF16_RELUMASK: `lb` holds the lane's
+// 16 mask bytes (loaded by the caller) and is applied to the accumulators as they are staged.
+// Either way the readback loop only writes C.
 template <int EPI, int NJ, bool F8 = false, int J0 = 0, int NJA = NJ, bool LANES = false>
 __device__ __forceinline__ void epi_tile_staged(const GemmArgs& a, const v4f (&acc)[4][NJA],
                                                 int m0, int n0, int split, char* region,
@@ -363,7 +465,9 @@ __device__ __forceinline__ void epi_tile_staged(const GemmArgs& a, const v4f (&a
                            (NJ == 4 || NJ == 8) && J0 % 4 == 0),
                 "lane-private mask: bf16 products, whole 64-row passes");
   const int g = lane >> 4, c = lane & 15;
-  if constexpr (EPI == EPI_BF16 || EPI == EPI_BF16_RELUMASK) {
+  if constexpr (LANES) {
+    epi_tile_lanes<EPI, NJ, J0, NJA>(a, acc, m0, n0, region, lane, lb);
+  } else if constexpr (EPI == EPI_BF16 || EPI == EPI_BF16_RELUMASK) {
     float bv[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -404,49 +508,28 @@ __device__ __forceinline__ void epi_tile_staged(const GemmArgs& a, const v4f (&a
         smj[j] = a.f8_sa_per_row ? a.f8_sa[m] : a.f8_sa[0];
       }
     }
-    constexpr bool LN_OUT = LANES && EPI == EPI_BF16, LN_IN = LANES && EPI == EPI_BF16_RELUMASK;
-    unsigned mw[NJ / 2 > 0 ? NJ / 2 : 1];   // LN_OUT: this call's dwords of the lane's mask
-#pragma unroll
-    for (int d = 0; d < NJ / 2; ++d) mw[d] = 0u;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int row = j * 16 + c;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        float a0 = acc[i][J0 + j][0], a1 = acc[i][J0 + j][1];
-        float a2 = acc[i][J0 + j][2], a3 = acc[i][J0 + j][3];
-        if constexpr (LN_IN) {   // masked accumulators become +0, which stores as bf16 +0
-          const unsigned w = lb[((J0 + j) >> 2) * 2 + (i >> 1)];
-          a0 = __uint_as_float(__float_as_uint(a0) & lane_mask_keep(w, i, J0 + j, 0));
-          a1 = __uint_as_float(__float_as_uint(a1) & lane_mask_keep(w, i, J0 + j, 1));
-          a2 = __uint_as_float(__float_as_uint(a2) & lane_mask_keep(w, i, J0 + j, 2));
-          a3 = __uint_as_float(__float_as_uint(a3) & lane_mask_keep(w, i, J0 + j, 3));
-        }
+        const float a0 = acc[i][J0 + j][0], a1 = acc[i][J0 + j][1];
+        const float a2 = acc[i][J0 + j][2], a3 = acc[i][J0 + j][3];
         float v0 = fmaf(a0, smj[j] * sn[i][0], bv[i][0]);
         float v1 = fmaf(a1, smj[j] * sn[i][1], bv[i][1]);
         float v2 = fmaf(a2, smj[j] * sn[i][2], bv[i][2]);
         float v3 = fmaf(a3, smj[j] * sn[i][3], bv[i][3]);
         if (relu) { v0 = relu_f(v0); v1 = relu_f(v1); v2 = relu_f(v2); v3 = relu_f(v3); }
-        const unsigned lo = (unsigned)f2bf(v0) | ((unsigned)f2bf(v1) << 16);
-        const unsigned hi = (unsigned)f2bf(v2) | ((unsigned)f2bf(v3) << 16);
-        if constexpr (LN_OUT) {
-          const int s = (i & 1) * 4 + ((J0 + j) & 3);
-          mw[(j >> 2) * 2 + (i >> 1)] |= (bf_pos_pair(lo) >> s) | (bf_pos_pair(hi) >> (8 + s));
-        }
+        const unsigned lo = f2bf_pk(v0, v1), hi = f2bf_pk(v2, v3);
         const int slot = i * 4 + g;  // 8-B slot of the 128-B row
         *(LDS_AS v2u*)(region + bf_stage_off(row, slot)) = (v2u){lo, hi};
       }
-    }
-    if constexpr (LN_OUT) {   // one coalesced store per lane: no cross-lane work, no byte stores
-      unsigned char* mp = a.mask_out + lane_mask_off(a.N, m0, n0, lane) + (J0 >> 2) * 8;
-      if constexpr (NJ == 8) *reinterpret_cast<v4u*>(mp) = (v4u){mw[0], mw[1], mw[2], mw[3]};
-      else *reinterpret_cast<v2u*>(mp) = (v2u){mw[0], mw[1]};
     }
     // aux rows (ReLU mask) for every readback row, in flight while the LDS writes drain
     const int q = lane & 7;
     uint4 hv[NJ * 2];
     unsigned hb[NJ * 2];
-    if constexpr (EPI == EPI_BF16_RELUMASK && !LN_IN) {
+    if constexpr (EPI == EPI_BF16_RELUMASK) {
       if (a.aux_bits) {
 #pragma unroll
         for (int it = 0; it < NJ * 2; ++it) {
@@ -483,7 +566,7 @@ __device__ __forceinline__ void epi_tile_staged(const GemmArgs& a, const v4f (&a
       const int m = m0 + row, n = n0 + q * 8;
       if (m < a.M && n < a.N) {
         uint4 o = make_uint4(v[0], v[1], v[2], v[3]);
-        if constexpr (EPI == EPI_BF16_RELUMASK && !LN_IN) {
+        if constexpr (EPI == EPI_BF16_RELUMASK) {
           // keep element e iff aux_e > 0 (bf16: sign clear and not +0), per 16-bit half
           // branch-free, both halves at once: bit 15 / 31 of p is set iff that bf16 half is in
           // [1, 0x7fff] (> 0; see the bitmask epilogue below), and (p << 1) - (p >> 15)
@@ -505,7 +588,7 @@ __device__ __forceinline__ void epi_tile_staged(const GemmArgs& a, const v4f (&a
           }
         }
         // (row-major mask) 1(y > 0) of the stored bf16, 8 bits per lane
-        if (!LN_OUT && EPI == EPI_BF16 && a.mask_out) {
+        if (EPI == EPI_BF16 && a.mask_out) {
           // branch-free: half h > 0 (bf16) <=> h in [1, 0x7fff] <=> bit 15 of
           // ((h & 0x7fff) + 0x7fff) & ~h; both halves at once (no carry: each sum <= 0xfffe),
           // then bits 15 / 31 of the 4 words gathered to bits 2e / 2e + 1 of one byte
@@ -700,20 +783,30 @@ __device__ __forceinline__ void epi_tile_staged(const GemmArgs& a, const v4f (&a
                 }
               }
               if (XB && a.cpl_gx_bf16) {
-                ushort4 gh;
-                gh.x = f2bf(gx[0]); gh.y = f2bf(gx[1]); gh.z = f2bf(gx[2]); gh.w = f2bf(gx[3]);
-                *reinterpret_cast<ushort4*>(reinterpret_cast<bf16_t*>(a.cpl_gx) +
-                                            (long)m * a.ld_cpl_gx + n) = gh;
+                *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(a.cpl_gx) +
+                                          (long)m * a.ld_cpl_gx + n) =
+                    make_uint2(f2bf_pk(gx[0], gx[1]), f2bf_pk(gx[2], gx[3]));
               } else {
                 *reinterpret_cast<float4*>(a.cpl_gx + (long)m * a.ld_cpl_gx + n) =
                     make_float4(gx[0], gx[1], gx[2], gx[3]);
               }
-              ushort4 d0, d1;
-              d0.x = f2bf(dsh[0]); d0.y = f2bf(dsh[1]); d0.z = f2bf(dsh[2]); d0.w = f2bf(dsh[3]);
-              d1.x = f2bf(d1v[0]); d1.y = f2bf(d1v[1]); d1.z = f2bf(d1v[2]); d1.w = f2bf(d1v[3]);
-              if (!F8 || a.cpl_dst) {   // null (e4m3 only): the e4m3 copy alone (MAF engine)
-                *reinterpret_cast<ushort4*>(drow + n) = d0;
-                *reinterpret_cast<ushort4*>(drow + a.cpl_dh + n) = d1;
+              // (packed conversion under XB only: the one-tile-per-block EPI_CPL_BWD kernels
+              // already spill, and spill 5 more registers with it)
+              if constexpr (XB) {
+                if (!F8 || a.cpl_dst) {   // null (e4m3 only): the e4m3 copy alone (MAF engine)
+                  *reinterpret_cast<uint2*>(drow + n) =
+                      make_uint2(f2bf_pk(dsh[0], dsh[1]), f2bf_pk(dsh[2], dsh[3]));
+                  *reinterpret_cast<uint2*>(drow + a.cpl_dh + n) =
+                      make_uint2(f2bf_pk(d1v[0], d1v[1]), f2bf_pk(d1v[2], d1v[3]));
+                }
+              } else {
+                ushort4 d0, d1;
+                d0.x = f2bf(dsh[0]); d0.y = f2bf(dsh[1]); d0.z = f2bf(dsh[2]); d0.w = f2bf(dsh[3]);
+                d1.x = f2bf(d1v[0]); d1.y = f2bf(d1v[1]); d1.z = f2bf(d1v[2]); d1.w = f2bf(d1v[3]);
+                if (!F8 || a.cpl_dst) {
+                  *reinterpret_cast<ushort4*>(drow + n) = d0;
+                  *reinterpret_cast<ushort4*>(drow + a.cpl_dh + n) = d1;
+                }
               }
               if (f8c && a.f8_cq) {
                 float f0[4], f1[4];

@@ -37,6 +37,15 @@ __device__ __forceinline__ bf16_t f2bf(float f) {
   return *reinterpret_cast<bf16_t*>(&h);
 }
 
+// Two floats -> one packed bf16 word (lo in bits 0..15, hi in 16..31) with a single
+// v_cvt_pk_bf16_f32: the instruction f2bf uses, so the same rounding (nearest even, NaN kept
+// quiet), without f2bf's dummy second operand and the shift + or that joins two results.
+__device__ __forceinline__ uint32_t f2bf_pk(float lo, float hi) {
+  typedef float v2f_ __attribute__((ext_vector_type(2)));
+  typedef __bf16 v2bf_ __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector((v2f_){lo, hi}, v2bf_));
+}
+
 // Store a float into a bf16 or fp32 "compute copy" buffer.
 template <typename T>
 __device__ __forceinline__ void st_cv(T* p, float v);

@@ -347,6 +347,8 @@ __device__ __forceinline__ void epi_coupling_fwd(const GemmArgs& a, const v4f (&
           const float sa = a.f8_sa[0];
           sv[0] = sa * sq[i].x; sv[1] = sa * sq[i].y; sv[2] = sa * sq[i].z; sv[3] = sa * sq[i].w;
         }
+        // (one f2bf at a time here: with the packed conversion the persistent instantiation, at
+        // the 256-VGPR limit, spills 4 registers and reloads them inside the K loop)
         const unsigned lo = (unsigned)f2bf(fmaf(acc[i][j][0], sv[0], bv[0])) |
                             ((unsigned)f2bf(fmaf(acc[i][j][1], sv[1], bv[1])) << 16);
         const unsigned hi = (unsigned)f2bf(fmaf(acc[i][j][2], sv[2], bv[2])) |
@@ -434,10 +436,10 @@ __device__ __forceinline__ void epi_coupling_fwd(const GemmArgs& a, const v4f (&
           }
           if (a.cf_yb && st_on) {
             uint4 o;
-            o.x = (unsigned)f2bf(y[0]) | ((unsigned)f2bf(y[1]) << 16);
-            o.y = (unsigned)f2bf(y[2]) | ((unsigned)f2bf(y[3]) << 16);
-            o.z = (unsigned)f2bf(y[4]) | ((unsigned)f2bf(y[5]) << 16);
-            o.w = (unsigned)f2bf(y[6]) | ((unsigned)f2bf(y[7]) << 16);
+            o.x = f2bf_pk(y[0], y[1]);
+            o.y = f2bf_pk(y[2], y[3]);
+            o.z = f2bf_pk(y[4], y[5]);
+            o.w = f2bf_pk(y[6], y[7]);
             *reinterpret_cast<uint4*>(a.cf_yb + (long)m * a.ld_cf_yb + jf) = o;
           }
           if (a.C && st_on)

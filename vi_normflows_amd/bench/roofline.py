@@ -77,8 +77,9 @@ LEVERS = {
         "operand delivery per CU (64 KiB per 32-deep K-tile pair at ~30 GB/s/CU, L2 hit ~0.75 "
         "from the 4x4 panel sharing); next: the 12.5 % padded tiles, a fifth LDS stage",
     "fwd NT EPI0 (bias+ReLU+bitmask)":
-        "per-CU LDS-DMA operand rate at K <= 1024 and the all-CU epilogue store burst; "
-        "next: overlap the C write with the next tile's main loop",
+        "per-CU LDS-DMA operand rate at K <= 1024, and an epilogue bound by VALU issue with "
+        "the MFMA pipe idle (its stores drain in 0.4 us of ~5 us); next: overlap a tile's "
+        "epilogue with another tile's main loop",
     "dgrad NT EPI2 (ReLU bitmask)":
         "same as the forward products (K = 800 / 1024)",
     "coupling fwd NT EPI5 (fused)":
